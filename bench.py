@@ -15,7 +15,11 @@ GPU; only its RANK / WORLD_SIZE / LOCAL_RANK / MASTER_PORT environment is used):
 step, the RCCL all-gather of the packed [obs | reward | discount | step_type] shards
 (dx_allgather_obs: librccl called from libdx).  No PyTorch.
 
-Prints ONE JSON line (rank 0).  Roofline accounting: DESIGN.md §5.4.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times `--steps` control
+steps, writes the last step's outputs if `--dump-outputs DIR` is given, and reports the
+headline with the timed region's health counters.  `--full` adds everything else: the
+step kernel's HIP-event launch time and the roofline built on it (oracle-counted FLOPs,
+DESIGN.md §5.4), the host-action call shape, and the CPU baselines.
 """
 
 from __future__ import annotations
@@ -45,9 +49,14 @@ def parse():
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--warmup", type=int, default=20)
     p.add_argument("--envs-per-gpu", type=int, default=4096)
-    p.add_argument("--cpu-seconds", type=float, default=12.0, help="bounded CPU-baseline sample (all threads)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--host-api-steps", type=int, default=50, help="extra line: the host-action call shape (0: off)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned (rank 0) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also: step-kernel launch time and roofline, host-action call shape, CPU baselines")
+    p.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: bounded CPU-baseline sample (all threads)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    p.add_argument("--host-api-steps", type=int, default=50,
+                   help="--full: extra line, the host-action call shape (0: off)")
     return p.parse_args()
 
 
@@ -206,6 +215,103 @@ def host_api_line(env, steps: int, warmup: int):
     }
 
 
+def full_extras(args, env, world: int, nsub: int, kernel_ms: float) -> dict:
+    """The result line's `--full` part, measured after the timed region: the roofline
+    of the step kernel's mean launch time `kernel_ms`, the host-action call shape and
+    the CPU baselines."""
+    import numpy as np
+
+    from dexterity_amd import _lib
+
+    B, ph = env.num_envs, env.physics
+    idx = np.linspace(0, B - 1, min(FLOP_SAMPLE_ENVS, B)).astype(int)
+    sample = [ph.get(f)[idx] for f in (_lib.QPOS, _lib.QVEL, _lib.QACC_WARMSTART, _lib.CTRL)]
+    by_stage = oracle_flops_per_env_step(sample, nsub)
+    flops = sum(v for k, v in by_stage.items() if k != "scan")
+    achieved_tf = flops * B / (kernel_ms * 1e-3) / 1e12
+    achieved_gbs = ALGO_BYTES_PER_ENV_STEP * B / (kernel_ms * 1e-3) / 1e9
+    traffic = None
+    pmc = os.path.join(ROOT, "profiles", "pmc_step_kernel.json")
+    if os.path.exists(pmc):
+        with open(pmc) as f:
+            p = json.load(f)
+        # only the build the PMC passes measured (profiles/pmc_step_kernel.json
+        # build_key = this library's dx_build_key); otherwise unmeasured
+        lib = _lib.load()
+        key = lib.dx_build_key().decode() if hasattr(lib, "dx_build_key") else None
+        if p.get("envs") == B and p.get("build_key") and p.get("build_key") == key:
+            traffic = p.get("hbm_bytes_per_launch")
+    host_api = host_api_line(env, args.host_api_steps, 5) if world == 1 and args.host_api_steps > 0 else None
+    cpu, extra = None, []
+    if world == 1 and not args.no_cpu_baseline:
+        gpu_states = [ph.get(f) for f in (_lib.QPOS, _lib.QVEL, _lib.QACC_WARMSTART)]
+        threads = host_threads()
+        cpu = cpu_baseline(args.cpu_seconds, threads, gpu_states, nsub)
+        one = [s[: max(8, B // 256)] for s in gpu_states]
+        extra.append(cpu_baseline(args.cpu_seconds / 3, 1, one, nsub))
+        extra.append(cpu_baseline_reach_1env(args.cpu_seconds / 3))
+    return {
+        # the path is FP32-VALU / latency bound (SURVEY.md §8 d3): the headline
+        # roofline is the oracle-counted FLOPs per env-step over the step kernel's
+        # mean launch time against the FP32 vector peak; HBM is the secondary block
+        "roofline": {
+            "bound": "valu_fp32",
+            "achieved": round(achieved_tf, 4),
+            "peak": FP32_PEAK_TFLOPS,
+            "unit": "TFLOP/s",
+            "frac": round(achieved_tf / FP32_PEAK_TFLOPS, 5),
+            "traffic": traffic,
+            "kernel": "dx_step_kernel",
+            "kernel_ms_avg": round(kernel_ms, 4),
+            "flops_per_env_step": round(flops),
+            "flops_by_stage": {k: round(v) for k, v in by_stage.items() if k != "scan"},
+            # the oracle's exhaustive hull scans, were they counted as work
+            "flops_per_env_step_full_hull_scan": round(flops + by_stage["scan"]),
+            "flops_sample": f"oracle stage counters over {len(idx)} env states of the GPU batch, {nsub} substeps; "
+                            "a mesh support is charged 16 vertices (an efficient support), not the full hull",
+            "hbm": {
+                "achieved": round(achieved_gbs, 3),
+                "peak": HBM_PEAK_GBS,
+                "unit": "GB/s",
+                "frac": round(achieved_gbs / HBM_PEAK_GBS, 6),
+                "algo_bytes_per_env_step": ALGO_BYTES_PER_ENV_STEP,
+                "traffic": traffic,
+            },
+        },
+        # the reference's call shape (host action in, host TimeStep out), beside the
+        # device-resident headline
+        "host_api": host_api,
+        "cpu_baseline": cpu,
+        "cpu_baseline_extra": extra,
+    }
+
+
+def dump_outputs(path: str, env, collator) -> None:
+    """What a caller of the timed path holds after its last step, as float32 .npy files:
+    the TimeStep of every env of this rank (the 123-float observation rows, reward,
+    discount, step_type), the physics state the step advanced (qpos, qvel) and, for a
+    sharded job, the gathered [obs | reward | discount | step_type] rows of all ranks.
+    4096 envs: 3.3 MB; the gathered rows of 8 x 4096 envs: 16.5 MB."""
+    import numpy as np
+
+    from dexterity_amd import _lib
+
+    os.makedirs(path, exist_ok=True)
+    ts = env.timestep()
+    arrays = {
+        "observation": np.concatenate([np.asarray(v).reshape(env.num_envs, -1) for v in ts.observation.values()], axis=1),
+        "reward": ts.reward,
+        "discount": ts.discount,
+        "step_type": ts.step_type,
+        "qpos": env.physics.get(_lib.QPOS),
+        "qvel": env.physics.get(_lib.QVEL),
+    }
+    if collator:
+        arrays["gathered"] = collator.read()
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     args = parse()
     rank = int(os.environ.get("RANK", "0"))
@@ -238,10 +344,11 @@ def main():
     if comm:
         comm.barrier()
     env.physics.health_clear()  # the timed region's own health counters
-    # the step kernel's mean launch time: HIP events around every 4th launch of the timed
-    # region (each bracket's two event packets cost ~5 us of the step they sit in)
-    _lib.check(L.dx_timing_enable(env.physics.ptr, 4))
-    _lib.check(L.dx_timing_read(env.physics.ptr, ctypes.byref(ctypes.c_double()), ctypes.byref(ctypes.c_int32())))
+    if args.full:
+        # the step kernel's mean launch time: HIP events around every 4th launch of the timed
+        # region (each bracket's two event packets cost ~5 us of the step they sit in)
+        _lib.check(L.dx_timing_enable(env.physics.ptr, 4))
+        _lib.check(L.dx_timing_read(env.physics.ptr, ctypes.byref(ctypes.c_double()), ctypes.byref(ctypes.c_int32())))
     t0 = time.perf_counter()
     for i in range(args.steps):
         one_step(args.warmup + i)
@@ -250,8 +357,9 @@ def main():
         comm.barrier()
     elapsed = time.perf_counter() - t0
     kt, kn = ctypes.c_double(), ctypes.c_int32()
-    _lib.check(L.dx_timing_read(env.physics.ptr, ctypes.byref(kt), ctypes.byref(kn)))
-    _lib.check(L.dx_timing_enable(env.physics.ptr, 0))
+    if args.full:
+        _lib.check(L.dx_timing_read(env.physics.ptr, ctypes.byref(kt), ctypes.byref(kn)))
+        _lib.check(L.dx_timing_enable(env.physics.ptr, 0))
     # a substep-queue timeout would mean corrupted hand-offs: no number is reported then
     qerr = env.physics.debug_get("queue_timeouts")
     refuse = "substep queue timed out during the timed region" if int(qerr[0]) != 0 else ""
@@ -278,37 +386,9 @@ def main():
         elapsed = comm.max(elapsed)
     total_env_steps = world * B * args.steps
     value = total_env_steps / elapsed
-    kernel_ms = kt.value / max(1, kn.value)
     if rank == 0:
-        import numpy as np
-
-        ph = env.physics
-        idx = np.linspace(0, B - 1, min(FLOP_SAMPLE_ENVS, B)).astype(int)
-        sample = [ph.get(f)[idx] for f in (_lib.QPOS, _lib.QVEL, _lib.QACC_WARMSTART, _lib.CTRL)]
-        by_stage = oracle_flops_per_env_step(sample, nsub)
-        flops = sum(v for k, v in by_stage.items() if k != "scan")
-        achieved_tf = flops * B / (kernel_ms * 1e-3) / 1e12
-        achieved_gbs = ALGO_BYTES_PER_ENV_STEP * B / (kernel_ms * 1e-3) / 1e9
-        traffic = None
-        pmc = os.path.join(ROOT, "profiles", "pmc_step_kernel.json")
-        if os.path.exists(pmc):
-            with open(pmc) as f:
-                p = json.load(f)
-            # only the build the PMC passes measured (profiles/pmc_step_kernel.json
-            # build_key = this library's dx_build_key); otherwise unmeasured
-            lib = _lib.load()
-            key = lib.dx_build_key().decode() if hasattr(lib, "dx_build_key") else None
-            if p.get("envs") == B and p.get("build_key") and p.get("build_key") == key:
-                traffic = p.get("hbm_bytes_per_launch")
-        host_api = host_api_line(env, args.host_api_steps, 5) if world == 1 and args.host_api_steps > 0 else None
-        cpu, extra = None, []
-        if world == 1 and not args.no_cpu_baseline:
-            gpu_states = [ph.get(f) for f in (_lib.QPOS, _lib.QVEL, _lib.QACC_WARMSTART)]
-            threads = host_threads()
-            cpu = cpu_baseline(args.cpu_seconds, threads, gpu_states, nsub)
-            one = [s[: max(8, B // 256)] for s in gpu_states]
-            extra.append(cpu_baseline(args.cpu_seconds / 3, 1, one, nsub))
-            extra.append(cpu_baseline_reach_1env(args.cpu_seconds / 3))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, env, collator)
         out = {
             "metric": "env-steps/sec (whole node), Shadow-hand cube reorient @4096 envs, 1/2/4/8 GPUs",
             "value": round(value, 1),
@@ -334,40 +414,10 @@ def main():
                 "physics_dt": 0.005,
                 "parallelism": f"env-sharded x{world}" + (", RCCL obs all-gather (libdx)" if world > 1 else ""),
             },
-            # the path is FP32-VALU / latency bound: the headline
-            # roofline is the oracle-counted FLOPs per env-step over the step kernel's
-            # mean launch time against the FP32 vector peak; HBM is the secondary block
-            "roofline": {
-                "bound": "valu_fp32",
-                "achieved": round(achieved_tf, 4),
-                "peak": FP32_PEAK_TFLOPS,
-                "unit": "TFLOP/s",
-                "frac": round(achieved_tf / FP32_PEAK_TFLOPS, 5),
-                "traffic": traffic,
-                "kernel": "dx_step_kernel",
-                "kernel_ms_avg": round(kernel_ms, 4),
-                "flops_per_env_step": round(flops),
-                "flops_by_stage": {k: round(v) for k, v in by_stage.items() if k != "scan"},
-                # the oracle's exhaustive hull scans, were they counted as work
-                "flops_per_env_step_full_hull_scan": round(flops + by_stage["scan"]),
-                "flops_sample": f"oracle stage counters over {len(idx)} env states of the GPU batch, {nsub} substeps; "
-                                "a mesh support is charged 16 vertices (an efficient support), not the full hull",
-                "hbm": {
-                    "achieved": round(achieved_gbs, 3),
-                    "peak": HBM_PEAK_GBS,
-                    "unit": "GB/s",
-                    "frac": round(achieved_gbs / HBM_PEAK_GBS, 6),
-                    "algo_bytes_per_env_step": ALGO_BYTES_PER_ENV_STEP,
-                    "traffic": traffic,
-                },
-            },
             "health": health,
-            # the reference's call shape (host action in, host TimeStep out), beside the
-            # device-resident headline
-            "host_api": host_api,
-            "cpu_baseline": cpu,
-            "cpu_baseline_extra": extra,
         }
+        if args.full:
+            out.update(full_extras(args, env, world, nsub, kt.value / max(1, kn.value)))
         print(json.dumps(out), flush=True)
     if collator:
         collator.close()
