@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <array>
 #include <map>
 #include <string>
 #include <vector>
@@ -520,6 +521,74 @@ extern "C" dx_model* dx_model_load(const void* blob, size_t nbytes) {
       }
     }
     m->hf["bpair_rec"] = br;
+    // Body-pair cull tables.  The units of a scene share a few bounding spheres (a palm
+    // cluster's ~15 partners meet the same cluster sphere, every cluster the same partner
+    // spheres) and one ground plane, so the kernel transforms each distinct one once per
+    // pass (dx_step.hip collision) and a unit only names its two:
+    //   bp_item [nbitem][2] float4, planes first then spheres, keyed on the float32 bits
+    //     the per-unit loop used to read: plane {point, geom}{normal, body | 1 << 16}
+    //     (its body's frame), sphere {centre, radius}{0, 0, 0, body};
+    //   bp_cull [nbpair] {item 1 | item 2 << 12 | flags, margin}: DX_CULL_PLANE item 1 is
+    //     a plane (plane test against sphere 2), DX_CULL_KEEP no sphere on a side (kept
+    //     without a test), neither: sphere test, then the box test of bpair_rec.
+    std::vector<float> items;
+    std::vector<int> cull(2 * std::max(nbp, 1), 0);
+    std::map<std::array<uint32_t, 5>, int> ids;
+    auto item_id = [&](bool plane, int key0, const float* key4, const float* a, const float* b, int body) {
+      std::array<uint32_t, 5> key;
+      key[0] = (uint32_t)key0 | (plane ? 0x80000000u : 0u);
+      memcpy(&key[1], key4, 16);
+      auto it = ids.find(key);
+      if (it != ids.end()) return it->second;
+      const int id = (int)ids.size();
+      ids[key] = id;
+      float e[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], 0.f};
+      const int tag = body | (plane ? 1 << 16 : 0);
+      memcpy(e + 7, &tag, 4);
+      items.insert(items.end(), e, e + 8);
+      return id;
+    };
+    const float zero4[4] = {0.f, 0.f, 0.f, 0.f};
+    int nplane = 0;
+    for (int pass = 0; pass < 2; pass++)  // planes take the first ids
+      for (int k = 0; k < nbp; k++) {
+        const float* s1 = bs.data() + 8 * k;
+        const float* s2 = s1 + 4;
+        const int pg = bpl[k];
+        const bool tested = s2[3] >= 0 && (pg >= 0 || s1[3] >= 0);
+        if (pass == 0) {
+          if (tested && pg >= 0) {
+            float pt[4] = {gp[3 * pg], gp[3 * pg + 1], gp[3 * pg + 2], 0.f};
+            const float nl[3] = {gm[9 * pg + 2], gm[9 * pg + 5], gm[9 * pg + 8]};
+            memcpy(pt + 3, &pg, 4);
+            item_id(true, pg, zero4, pt, nl, gb[pg]);
+          }
+          nplane = (int)ids.size();
+          continue;
+        }
+        int w = DX_CULL_KEEP;
+        if (tested) {
+          const int i2 = item_id(false, bb[2 * k + 1], s2, s2, zero4, bb[2 * k + 1]);
+          float pt[4] = {0.f, 0.f, 0.f, 0.f};
+          const int i1 = pg >= 0 ? item_id(true, pg, zero4, pt, zero4, 0)  // (found: pass 0 made it)
+                                 : item_id(false, bb[2 * k], s1, s1, zero4, bb[2 * k]);
+          w = i1 | (i2 << 12) | (pg >= 0 ? DX_CULL_PLANE : 0);
+        }
+        cull[2 * k] = w;
+        memcpy(&cull[2 * k + 1], &pm[ba[k]], 4);
+      }
+    d.nbitem = (int)ids.size();
+    d.nbplane = nplane;
+    // world-space items live in the narrowphase's portal area while the pairs are tested:
+    // one float4 per item and a second one per plane
+    if (d.nbitem + d.nbplane > DX_NGRP_MAX * 36 / 4) {
+      fail(DX_ELIMIT, "distinct broadphase spheres and planes exceed the LDS item area");
+      delete m;
+      return nullptr;
+    }
+    if (items.empty()) items.assign(8, 0.f);
+    m->hf["bp_item"] = items;
+    m->hi["bp_cull"] = cull;
   }
   // tree records: per body (lane = body in the level loops) and per dof, so a stage
   // loads its model data in one memory round trip instead of a chain per tree level
@@ -901,7 +970,7 @@ static int device_model(dx_model* m, int device, DevModel* out) {
   UF(geom_size); UF(geom_pos); UF(geom_mat); UF(geom_center); UF(geom_bsphere); UF(geom_bsphere_b); UF(geom_obb_b);
   UI(mesh_vertadr); UI(mesh_vertnum); UF(mesh_vert4);
   UI(mesh_binn); UI(mesh_bincap); UI(mesh_binadr); UF(mesh_bin4);
-  UF(geom_rec); UF(gpair_rec); UF(geom_crec); UF(bpair_rec); UF(body_rec); UF(dof_rec); UI(ldl_tab);
+  UF(geom_rec); UF(gpair_rec); UF(geom_crec); UF(bpair_rec); UF(bp_item); UI(bp_cull); UF(body_rec); UF(dof_rec); UI(ldl_tab);
   UI(site_bodyid); UF(site_pos); UF(site_mat);
   UI(tendon_adr); UI(tendon_num); UI(wrap_dof); UI(wrap_qadr); UI(limt_ten);
   UF(tendon_range); UF(tendon_margin); UF(tendon_solref); UF(tendon_solimp); UF(tendon_invweight0);
@@ -1556,6 +1625,21 @@ extern "C" int dx_debug_get(dx_batch* b, const char* name, float* dst, size_t nf
   if (std::string(name) == "queue_slots") {  // int32 bits: the queued launch's persistent workgroups
     if (nfloats < 1) return fail(DX_EINVAL, "destination too small");
     memcpy(dst, &b->slots, 4);
+    return 0;
+  }
+  // the body-pair cull's host tables (dx_model_load): their sizes {nbitem, nbplane, nbpair}
+  // as int32 bits, bp_item [nbitem][8] floats, bp_cull [nbpair][2] int32 bits
+  if (std::string(name) == "bp_sizes") {
+    if (nfloats < 3) return fail(DX_EINVAL, "destination too small");
+    const int v[3] = {b->dm.nbitem, b->dm.nbplane, b->dm.nbpair};
+    memcpy(dst, v, sizeof(v));
+    return 0;
+  }
+  if (std::string(name) == "bp_item" || std::string(name) == "bp_cull") {
+    const bool item = std::string(name) == "bp_item";
+    const size_t n = item ? (size_t)8 * b->dm.nbitem : (size_t)2 * b->dm.nbpair;
+    if (nfloats < n) return fail(DX_EINVAL, "destination too small");
+    if (n) memcpy(dst, item ? (const void*)b->model->hf.at("bp_item").data() : (const void*)b->model->hi.at("bp_cull").data(), n * 4);
     return 0;
   }
   if (!b->debug) return fail(DX_EINVAL, "debug not enabled");

@@ -58,6 +58,9 @@
 // more than 8 candidates (dx_step.hip narrow_pass); the LDS layout reserves the portal
 // points of the larger count
 #define DX_NGRP_MAX 16
+// bp_cull word 0: item 1 (bits 0-11) | item 2 (bits 12-23) | flags
+#define DX_CULL_PLANE (1 << 30)       // item 1 is a plane: plane test against sphere 2
+#define DX_CULL_KEEP ((int)0x80000000)  // no sphere on a side: kept without a test
 #define DX_GOAL_RETRIES 64  // reach goal sampling: GoalInitializationError retries per goal (bounded)
 
 enum { DXG_PLANE = 0, DXG_SPHERE = 2, DXG_CAPSULE = 3, DXG_BOX = 6, DXG_MESH = 7 };
@@ -107,6 +110,11 @@ struct DevModel {
   const DXG float4 *geom_rec, *gpair_rec;
   // culling records (dx_api.hip): geom_crec [ngeom][6], bpair_rec [nbpair][7] float4
   const DXG float4 *geom_crec, *bpair_rec;
+  // body-pair cull (dx_api.hip): bp_item [nbitem][2] float4, the distinct planes (the first
+  // nbplane) and bounding spheres of the body pairs; bp_cull [nbpair], a pair's two items
+  const DXG float4* bp_item;
+  const DXG int2* bp_cull;
+  int nbitem, nbplane;
   // tree records (dx_api.hip): body_rec [nbody][8] float4, dof_rec [nv][2] float4
   const DXG float4 *body_rec, *dof_rec;
   // tree-sparse LDL^T of M (dx_api.hip): [ldl_nslot][64] items k | i << 8 | j << 16

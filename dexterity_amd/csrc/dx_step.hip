@@ -1151,63 +1151,112 @@ __device__ __forceinline__ void collision(const Ctx& c, int watch_only, int wg, 
     nsl = 0;
     SYNC();
   };
-  // the next chunk's records are loaded while this chunk is tested (one memory
-  // round trip in flight across chunk boundaries)
-  float4 nx[6];
+  // The pairs of a scene share a few bounding spheres and one ground plane (dx_api.hip
+  // bp_item), so each distinct one goes to the world once per pass, lane per item, into
+  // the narrowphase's portal area -- unused until the narrowphase, between the lists
+  // flush() writes and sl: item i at float4 i (a sphere's centre and radius, a plane's
+  // point and body), plane i's normal at float4 nbitem + i.
+  float4* witem = (float4*)c.f(c.L.cand + c.L.cand_max);
+  const int nitem = m.nbitem;
   // the observation pass's watch test walks only the body pairs that can hold the
   // watched contact (dx_set_watch builds that list on the host)
   const int nloop = (watch_only && wlist) ? wn : c.nbpair;
   auto bpidx = [&](int i) { return (watch_only && wlist) ? wlist[i] : i; };
-  {
-    const int i0 = max(min(LANE, nloop - 1), 0);
-    const DXG float4* R = m.bpair_rec + 7 * (nloop > 0 ? bpidx(i0) : 0);
+  // A pair names its two items and carries its margin (bp_cull, 8 B): the records of the
+  // next DX_CULL_AHEAD chunks are loaded while this group of chunks is tested, and the
+  // first group's with the items, in one memory round trip.
+  constexpr int DX_CULL_AHEAD = 4;
+  int2 nx[DX_CULL_AHEAD];
+  auto load = [&](int g0) {
 #pragma unroll
-    for (int k = 0; k < 6; k++) nx[k] = R[k];
-  }
-  for (int base = 0; base < nloop; base += DX_WAVE) {
-    const int bp = base + LANE < nloop ? bpidx(base + LANE) : c.nbpair;
-    bool keep = false, box = false;
-    const float4 r0 = nx[0], s1 = nx[1], s2 = nx[2], r3 = nx[3], r4 = nx[4], r5 = nx[5];
-    if (base + DX_WAVE < nloop) {
-      const DXG float4* R = m.bpair_rec + 7 * bpidx(min(base + DX_WAVE + LANE, nloop - 1));
-#pragma unroll
-      for (int k = 0; k < 6; k++) nx[k] = R[k];
+    for (int k = 0; k < DX_CULL_AHEAD; k++) {
+      const int i = g0 + k * DX_WAVE + LANE;
+      nx[k] = m.bp_cull[i < nloop ? bpidx(i) : 0];
     }
-    if (bp < c.nbpair) {
-      int b1 = __float_as_int(r0.x), b2 = __float_as_int(r0.y);
-      keep = true;
-      if (watch_only) keep = (b2 == wb || b1 == wb) && (m.geom_bodyid[wg] == b1 || m.geom_bodyid[wg] == b2);
-      float mg = r3.x;
-      int pg = __float_as_int(r3.y);
-      if (keep && s2.w >= 0) {
-        float c2[3];
-        const float s2v[3] = {s2.x, s2.y, s2.z};
-        matvec3(c2, xmat + 9 * b2, s2v);
-        for (int k = 0; k < 3; k++) c2[k] += xpos[3 * b2 + k];
-        if (pg >= 0) {
-          int pb = __float_as_int(r3.z);
-          const float pl[3] = {r4.x, r4.y, r4.z}, nl[3] = {r5.x, r5.y, r5.z};
-          float pp[3], n[3];
-          matvec3(pp, xmat + 9 * pb, pl);
-          matvec3(n, xmat + 9 * pb, nl);
-          float rr[3] = {c2[0] - pp[0] - xpos[3 * pb], c2[1] - pp[1] - xpos[3 * pb + 1], c2[2] - pp[2] - xpos[3 * pb + 2]};
-          keep = dot3(rr, n) <= s2.w + mg;
-        } else if (s1.w >= 0) {
-          float c1[3];
-          const float s1v[3] = {s1.x, s1.y, s1.z};
-          matvec3(c1, xmat + 9 * b1, s1v);
-          for (int k = 0; k < 3; k++) c1[k] += xpos[3 * b1 + k];
-          keep = sphere_overlap(c1, s1.w, c2, s2.w, mg);
-          box = true;
-        }
+  };
+  float4 ia, ib4;
+  auto item_load = [&](int base) {
+    const int i = max(min(base + LANE, nitem - 1), 0);
+    ia = m.bp_item[2 * i];
+    ib4 = m.bp_item[2 * i + 1];
+  };
+  // (whole 16-B loads, complete here: not split and sunk into the branches that use them)
+#define DX_PIN4(v) asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w))
+  load(0);
+  item_load(0);
+#pragma unroll
+  for (int k = 0; k < DX_CULL_AHEAD; k++) asm volatile("" : "+v"(nx[k].x), "+v"(nx[k].y));
+  DX_PIN4(ia);
+  DX_PIN4(ib4);
+  for (int base = 0; base < nitem; base += DX_WAVE) {
+    const int i = base + LANE;
+    if (base) {
+      item_load(base);
+      DX_PIN4(ia);
+      DX_PIN4(ib4);
+    }
+    if (i < nitem) {
+      const float4 a = ia, b = ib4;
+      const int tag = __float_as_int(b.w), ib = tag & 0xffff;
+      const float av[3] = {a.x, a.y, a.z};
+      float w[3];
+      matvec3(w, xmat + 9 * ib, av);
+      if (tag >> 16) {
+        const float nl[3] = {b.x, b.y, b.z};
+        float n[3];
+        matvec3(n, xmat + 9 * ib, nl);
+        witem[i] = make_float4(w[0], w[1], w[2], __int_as_float(ib));
+        witem[nitem + i] = make_float4(n[0], n[1], n[2], 0.f);
+      } else {
+        for (int k = 0; k < 3; k++) w[k] += xpos[3 * ib + k];
+        witem[i] = make_float4(w[0], w[1], w[2], a.w);
       }
     }
-    uint64_t mask = __ballot(keep);
-    int pos = __popcll(mask & ((1ull << LANE) - 1ull));
-    if (keep) sl[nsl + pos] = box ? (bp | (int)0x80000000) : bp;
-    nsl += __popcll(mask);
-    SYNC();
-    if (nsl > slcap - DX_WAVE) flush();
+  }
+#undef DX_PIN4
+  SYNC();
+  for (int g0 = 0; g0 < nloop; g0 += DX_CULL_AHEAD * DX_WAVE) {
+    int2 cur[DX_CULL_AHEAD];
+#pragma unroll
+    for (int k = 0; k < DX_CULL_AHEAD; k++) cur[k] = nx[k];
+    if (g0 + DX_CULL_AHEAD * DX_WAVE < nloop) load(g0 + DX_CULL_AHEAD * DX_WAVE);
+#pragma unroll
+    for (int k = 0; k < DX_CULL_AHEAD; k++) {
+      const int base = g0 + k * DX_WAVE;
+      if (base >= nloop) break;
+      const int bp = base + LANE < nloop ? bpidx(base + LANE) : c.nbpair;
+      bool keep = false, box = false;
+      if (bp < c.nbpair) {
+        const int w = cur[k].x;
+        const float mg = __int_as_float(cur[k].y);
+        keep = true;
+        if (watch_only && !wlist) {
+          const int b1 = m.bpair_body[2 * bp], b2 = m.bpair_body[2 * bp + 1];
+          keep = (b2 == wb || b1 == wb) && (m.geom_bodyid[wg] == b1 || m.geom_bodyid[wg] == b2);
+        }
+        if (keep && w >= 0) {  // (DX_CULL_KEEP is the sign bit)
+          const float4 s1 = witem[w & 0xfff], s2 = witem[(w >> 12) & 0xfff];
+          const float c2[3] = {s2.x, s2.y, s2.z};
+          if (w & DX_CULL_PLANE) {
+            const float4 nw = witem[nitem + (w & 0xfff)];
+            const int pb = __float_as_int(s1.w);
+            const float n[3] = {nw.x, nw.y, nw.z};
+            float rr[3] = {c2[0] - s1.x - xpos[3 * pb], c2[1] - s1.y - xpos[3 * pb + 1], c2[2] - s1.z - xpos[3 * pb + 2]};
+            keep = dot3(rr, n) <= s2.w + mg;
+          } else {
+            const float c1[3] = {s1.x, s1.y, s1.z};
+            keep = sphere_overlap(c1, s1.w, c2, s2.w, mg);
+            box = true;
+          }
+        }
+      }
+      uint64_t mask = __ballot(keep);
+      int pos = __popcll(mask & ((1ull << LANE) - 1ull));
+      if (keep) sl[nsl + pos] = box ? (bp | (int)0x80000000) : bp;
+      nsl += __popcll(mask);
+      SYNC();
+      if (nsl > slcap - DX_WAVE) flush();
+    }
   }
   flush();
   if (nbc > half) { nbc = half; if (LANE == 0) I[I_OVF] |= 1; }

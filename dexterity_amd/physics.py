@@ -180,6 +180,16 @@ class BatchedPhysics:
             out = np.zeros(1, dtype=np.int32)
             _lib.check(_lib.load().dx_debug_get(self.ptr, name.encode(), out.ctypes.data, 1))
             return out
+        if name in ("bp_sizes", "bp_item", "bp_cull"):
+            # the body-pair cull's host tables (dx_api.hip): {nbitem, nbplane, nbpair}, the
+            # distinct planes and spheres [nbitem][8], a pair's items and margin [nbpair][2]
+            out = np.zeros(3, dtype=np.int32)
+            _lib.check(_lib.load().dx_debug_get(self.ptr, b"bp_sizes", out.ctypes.data, 3))
+            if name == "bp_sizes":
+                return out
+            out = np.zeros((out[0], 8), np.float32) if name == "bp_item" else np.zeros((out[2], 2), np.int32)
+            _lib.check(_lib.load().dx_debug_get(self.ptr, name.encode(), out.ctypes.data, out.size))
+            return out
         shape = sizes[name]
         out = np.empty(shape, dtype=np.float32)
         _lib.check(_lib.load().dx_debug_get(self.ptr, name.encode(), out.ctypes.data, out.size))
