@@ -17,6 +17,20 @@ __device__ __forceinline__ int lane_id() {
   return l;
 }
 #define LANE (lane_id())
+// The laundering also hides the lane id's range, so a guard that a constant n and the
+// lane's half decide stays a compare and an exec-mask block of its own.  lane_ranged()
+// states the range again (no instruction); lane_clamped(n) is the lane's index into n
+// entries for a load that every lane issues and selects after (n == 0 reads entry 0).
+// Not the default LANE: with the range known a `for (i = LANE; i < n; i += DX_WAVE)` over
+// a constant n becomes straight-line code, and the compiler then contracts other
+// multiply-add pairs around it -- the specialized kernels' results change in the last bit
+// ("lane guards").
+__device__ __forceinline__ int lane_ranged() {
+  const int l = lane_id();
+  __builtin_assume((unsigned)l < (unsigned)DX_WAVE);
+  return l;
+}
+__device__ __forceinline__ int lane_clamped(int n) { return min(lane_id(), max(n - 1, 0)); }
 // A workgroup is exactly one wavefront, and a wavefront's LDS instructions execute
 // in issue order, so cross-lane LDS hand-offs need only a compiler-level barrier
 // (no s_barrier, and no s_waitcnt on outstanding global stores).
@@ -675,7 +689,7 @@ __device__ __forceinline__ void crb_mass(const Ctx& c) {
   // (a load after a barrier is a full round trip on the wave's critical path)
   BodyRec br;
   const bool act = load_body(c, br);
-  const int i0 = min(LANE, nv - 1);  // nv <= 64 (model check): one dof per lane
+  const int i0 = lane_clamped(nv);  // nv <= 64 (model check): one dof per lane
   const float4 d0r = m.dof_rec[2 * i0], d1r = m.dof_rec[2 * i0 + 1];
   for (int k = LANE; k < 10 * c.nbody; k += DX_WAVE) crb[k] = cinert[k];
   for (int k = LANE; k < ti(nv); k += DX_WAVE) M[k] = 0;
@@ -992,7 +1006,7 @@ __device__ __forceinline__ void mfma_chol_solve64(const float* A, int n, float d
 // transpose).  A (+ dj on the diagonal) -> x = A^-1 x.  tests/test_sweep_solve.py
 // restates it in numpy.
 __device__ __forceinline__ void mfma_sweep_solve30(const float* A, int n, float dj, float* x) {
-  const int l = LANE;
+  const int l = lane_ranged();  // (hi is 0 or 1: with a constant n the row guards below fold)
   const int j = l & 31, hi = l >> 5;
   // Every lane loads in-range addresses (indices clamped to n - 1) and selects after:
   // a guarded load compiles to an exec-mask branch with its own LDS wait, 32 in a row.
@@ -1061,13 +1075,17 @@ __device__ __forceinline__ void mfma_sweep_solve30(const float* A, int n, float 
     C[vk + 1] = ph ? 0.f : C[vk + 1];
     C = __builtin_amdgcn_mfma_f32_32x32x2f32(-a, b, C, 0, 0, 0);
   }
-  // column 31 -> x (lane 31 of each half writes its half's rows)
+  // column 31 -> x (lane 31 of each half writes its half's rows).  One guard for the 16
+  // stores: they run from the highest row down, and a row past n goes to the slot of the
+  // lane's first row, which the lane's last store (v = 0) then fills with its own value
+  // (one lane's LDS stores land in program order).
   SYNC();
-  if (j == 31) {
+  if (j == 31 && 4 * hi < n) {
+    float* xh = x + 4 * hi;
 #pragma unroll
-    for (int v = 0; v < 16; v++) {
-      const int i = 8 * (v >> 2) + 4 * hi + (v & 3);
-      if (i < n) x[i] = C[v];
+    for (int v = 15; v >= 0; v--) {
+      const int o = 8 * (v >> 2) + (v & 3);  // the row less 4 hi
+      xh[o + 4 * hi < n ? o : 0] = C[v];
     }
   }
   SYNC();
@@ -1079,7 +1097,7 @@ __device__ __forceinline__ void mfma_sweep_solve30(const float* A, int n, float 
 // written to Ainv as a packed lower triangle (may not alias A).  For repeated solves with
 // one matrix: CG's M^-1 grad, one matrix-vector product per iteration instead of a sweep.
 __device__ __forceinline__ void mfma_sweep_inverse30(const float* A, int n, float* Ainv) {
-  const int l = LANE;
+  const int l = lane_ranged();
   const int j = l & 31, hi = l >> 5;
   const int jc = min(j, n - 1);
   float av[16];

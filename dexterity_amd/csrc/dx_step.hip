@@ -744,24 +744,15 @@ __device__ __forceinline__ int mpr_step(const Shape& G, MprState& S, float& dept
   const int slot = (ph == 0 || swap || x1) ? 1 : (ph == 1 || x2) ? 2 : 3;
   if (ph >= 0) mp_st(P + 9 * slot, p);
   if (rr) mp_st(P + (r2 ? 18 : 9), p);
-  // phase bookkeeping
-  if (ph == -1) {
-    S.phase = 0;
-  } else if (ph == 0) {
-    S.phase = 1;
-  } else if (ph == 1) {
-    S.phase = 2;
-    S.it = 0;
-  } else if (ph == 2) {
-    S.it++;
-    if (!rr) {
-      S.phase = dot3(dir, v1) >= 0 ? 4 : 3;
-      S.it = 0;
-    }
-  } else {
-    S.it++;
-    if (ph == 3 && dot3(dir, v1) >= 0) { S.phase = 4; S.it = 0; }
-  }
+  // phase bookkeeping, as selects (an if chain here is five exec-mask blocks of one or two
+  // moves each, on every trip): -1 -> 0 -> 1 -> 2 (it = 0); 2 counts its trips and goes on
+  // to 3 or 4 (it = 0) once p replaced neither P1 nor P2; 3 counts and goes on to 4
+  // (it = 0) when the origin is on dir's side; 4 counts
+  const bool fwd = dot3(dir, v1) >= 0;
+  const bool adv = (ph == 2 && !rr) || (ph == 3 && fwd);
+  const int it1 = S.it + 1;
+  S.phase = ph < 2 ? ph + 1 : adv ? (ph == 2 && !fwd ? 3 : 4) : ph;
+  S.it = (ph == 1 || adv) ? 0 : ph >= 2 ? it1 : S.it;
   return 0;
 }
 
