@@ -38,7 +38,7 @@ EXPORTS = (
     "dx_env_set_time_limit", "dx_set_outputs", "dx_env_create_shard",
     "dx_health", "dx_health_clear", "dx_ncon_histogram", "dx_env_set_goal_time_limit",
     "dx_env_step_random", "dx_env_save", "dx_env_load", "dx_env_state_field", "dx_env_step_host",
-    "dx_build_key",
+    "dx_build_key", "dx_env_set_action_filter", "dx_env_action_noise_draw",
 )
 COMM_ID_BYTES = 128
 STAGES = ("kinematics", "crb", "broadphase", "midphase", "narrowphase", "constraints", "velocity",
@@ -51,6 +51,8 @@ NSTAGE = 48
 # the narrowphase trip's parts (DX_NP_MARKS builds only)
 NP_STAGES = {36: "np_loop", 37: "np_fresh", 38: "np_supload", 39: "np_supred", 40: "np_portal"}
 OUT_OBS, OUT_REWARD, OUT_DISCOUNT, OUT_STEP_TYPE, OUT_GOAL, OUT_SUCCESSES, OUT_GOAL_FAILURES, OUT_GOAL_QPOS = range(8)
+OUT_PREV_ACTION = 8
+ACT_NOISE, ACT_SMOOTH, ACT_PREVIOUS = 1, 2, 4  # dx_action_filter.flags
 TASK_REORIENT, TASK_REACH, TASK_HANDOVER = 0, 1, 2
 REACH_NPARAMS_HEAD = 26
 
@@ -74,6 +76,17 @@ class IkOptions(ctypes.Structure):
         ("num_attempts", ctypes.c_int32),
         ("stop_on_first", ctypes.c_int32),
         ("seed", ctypes.c_uint64),
+    ]
+
+
+class ActionFilter(ctypes.Structure):
+    """struct dx_action_filter (include/dx.h)."""
+
+    _fields_ = [
+        ("flags", ctypes.c_int32),
+        ("noise_scale", ctypes.c_float),
+        ("smooth_alpha", ctypes.c_double),
+        ("noise_seed", ctypes.c_uint64),
     ]
 
 
@@ -155,6 +168,9 @@ def load(path: str = LIB_PATH):
     L.dx_env_pack_outputs.argtypes = [vp, vp]
     if hasattr(L, "dx_env_step_host"):  # (round 6; an older variant library for A/B lacks it)
         L.dx_env_step_host.argtypes = [vp, vp, vp]
+    if hasattr(L, "dx_env_set_action_filter"):  # (an older variant library for A/B lacks the action pipeline)
+        L.dx_env_set_action_filter.argtypes = [vp, ctypes.POINTER(ActionFilter)]
+        L.dx_env_action_noise_draw.argtypes = [vp, i32, vp]
     L.dx_timing_enable.argtypes = [vp, ctypes.c_int]
     L.dx_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i32)]
     L.dx_stage_timing.argtypes = [vp, ctypes.c_int]

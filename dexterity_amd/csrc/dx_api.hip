@@ -1668,13 +1668,18 @@ extern "C" __global__ void dx_task_pre_kernel(TaskParams P, TaskState S, DevBatc
 extern "C" __global__ void dx_task_post_kernel(TaskParams P, TaskState S, DevBatch B);
 extern "C" __global__ void dx_mt_seed_kernel(int nenv, uint64_t seed, uint32_t* mt_env, uint32_t* mt_goal);
 extern "C" __global__ void dx_mtw_seed_kernel(int nenv, uint64_t seed, uint32_t* mt);
+extern "C" __global__ void dx_action_filter_kernel(ActFilter F, const float* action);
+extern "C" __global__ void dx_action_noise_draw_kernel(int nenv, int n, uint32_t* mt, double* out);
 
 struct dx_env {
   dx_batch* batch;
   TaskParams P;
   TaskState S;
   int nsub;
-  std::vector<void*> allocs;
+  std::vector<void*> allocs;  // positional: [0] the action buffer, [1] the packed outputs
+  // the action pipeline (dx_env_set_action_filter): off while F.flags == 0; its buffers
+  // (F.mt != nullptr once allocated) are the batch's
+  ActFilter F{};
 };
 
 extern "C" dx_env* dx_env_create(const dx_model* m, int32_t nenv, int32_t device, int32_t task,
@@ -1860,6 +1865,24 @@ extern "C" __global__ void dx_sample_actions_kernel(int nenv, int nu, const floa
 static int env_run(dx_env* e, const float* action, bool random = false, uint64_t seed = 0, int step = 0) {
   dx_batch* b = e->batch;
   HIPCHK(hipSetDevice(b->device));
+  if (e->F.flags && (action || random)) {
+    // the action pipeline: one launch ahead of the step's, which then read the filtered
+    // buffer (never the caller's); the random agent draws into the action buffer first --
+    // the same function of (seed, env, step) as the step kernel's own draw
+    if (random) {
+      void* buf = nullptr;
+      if (int rc = dx_env_action_buffer(e, &buf)) return rc;
+      hipLaunchKernelGGL(dx_sample_actions_kernel, dim3((e->P.nenv * e->P.nu + 255) / 256), dim3(256), 0, b->stream,
+                         e->P.nenv, e->P.nu, b->dm.actuator_ctrlrange, seed, step, e->P.env0, (float*)buf);
+      HIPCHK(hipGetLastError());
+      action = (const float*)buf;
+      random = false;
+    }
+    hipLaunchKernelGGL(dx_action_filter_kernel, dim3((e->P.nenv + DX_ACT_WAVES - 1) / DX_ACT_WAVES),
+                       dim3(DX_WAVE * DX_ACT_WAVES), 0, b->stream, e->F, action);
+    HIPCHK(hipGetLastError());
+    action = e->F.out;
+  }
   const bool fuse = !getenv("DX_NO_FUSE") && ((e->P.kind != DX_KIND_REACH && b->db.defer) ||
                                               (e->P.kind == DX_KIND_REACH && b->spec >= 0 && dx_spec_reach(b->spec)));
   if (fuse) {
@@ -1905,8 +1928,92 @@ extern "C" int dx_env_reset(dx_env* e) {
   // step_type LAST makes the pre-kernel run initialize_episode for every env
   std::vector<int> last(e->P.nenv, 2);
   HIPCHK(hipMemcpyAsync(e->S.step_type, last.data(), last.size() * 4, hipMemcpyHostToDevice, e->batch->stream));
+  if (e->F.flags) {  // the action pipeline's initialize_episode: no draw, no EMA value, zero previous action
+    const size_t E = e->P.nenv;
+    HIPCHK(hipMemsetAsync(e->F.ema_set, 0, E * 4, e->batch->stream));
+    HIPCHK(hipMemsetAsync(e->F.prev, 0, E * e->P.nu * 4, e->batch->stream));
+  }
   HIPCHK(hipStreamSynchronize(e->batch->stream));
   return env_run(e, nullptr);
+}
+
+// ------------------------------------------------------------------------ //
+// the action pipeline (dx_task.hip dx_action_filter_kernel)
+// ------------------------------------------------------------------------ //
+extern "C" int dx_env_set_action_filter(dx_env* e, const dx_action_filter* f) {
+  if (!e) return fail(DX_EINVAL, "null env");
+  dx_batch* b = e->batch;
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));  // may be called between steps
+  const int flags = f ? f->flags : 0;
+  if (flags & ~(DX_ACT_NOISE | DX_ACT_SMOOTH | DX_ACT_PREVIOUS)) return fail(DX_EINVAL, "unknown action filter flags");
+  ActFilter& F = e->F;
+  if (!flags) {  // off: the step's launches, outputs and checkpoint are those of an env never configured
+    F.flags = 0;
+    return 0;
+  }
+  const int nu = e->P.nu;
+  const size_t E = e->P.nenv;
+  if (nu > DX_ACT_NU_MAX) return fail(DX_ELIMIT, "action filter: more than 64 actuators");
+  if (nu < 1) return fail(DX_EINVAL, "action filter: the model has no actuators");
+  if ((flags & DX_ACT_SMOOTH) && !(f->smooth_alpha >= 0.0 && f->smooth_alpha <= 1.0))
+    return fail(DX_EINVAL, "action filter: smooth_alpha must be within [0, 1]");
+  if (flags & DX_ACT_NOISE) {
+    if (!std::isfinite(f->noise_scale) || f->noise_scale < 0.f)
+      return fail(DX_EINVAL, "action filter: noise_scale must be finite and non-negative");
+    // the reference's stddev, scale * (maximum - minimum), is infinite for an unbounded actuator
+    const auto& lim = b->model->hi.at("actuator_ctrllimited");
+    for (int i = 0; i < nu; i++)
+      if (i >= (int)lim.size() || !lim[i]) return fail(DX_EINVAL, "action filter: noise needs every actuator ctrllimited");
+  }
+  if (!F.mt) {  // first use (balloc zeroes: no EMA value, zero previous action)
+    ActFilter A{};
+    int rc = balloc(b, (void**)&A.out, E * nu * 4);
+    if (!rc) rc = balloc(b, (void**)&A.ema, E * nu * 4);
+    if (!rc) rc = balloc(b, (void**)&A.prev, E * nu * 4);
+    if (!rc) rc = balloc(b, (void**)&A.ema_set, E * 4);
+    if (!rc) rc = balloc(b, (void**)&A.mt, E * DX_MTW_WORDS * 4);
+    if (rc) return rc;
+    A.nenv = e->P.nenv;
+    A.nu = nu;
+    A.ctrlrange = (const float*)b->dm.actuator_ctrlrange;
+    A.step_type = e->S.step_type;
+    A.episode = e->S.episode;
+    F = A;
+  } else {
+    // a stage switched on again starts as at initialize_episode
+    if (!F.flags) HIPCHK(hipMemsetAsync(F.prev, 0, E * nu * 4, b->stream));
+    if (!(F.flags & DX_ACT_SMOOTH)) HIPCHK(hipMemsetAsync(F.ema_set, 0, E * 4, b->stream));
+  }
+  if (flags & DX_ACT_NOISE) {  // env e draws from RandomState(noise_seed + env0 + e)
+    hipLaunchKernelGGL(dx_mtw_seed_kernel, dim3((e->P.nenv + 63) / 64), dim3(64), 0, b->stream, e->P.nenv,
+                       f->noise_seed + (uint64_t)e->P.env0, F.mt);
+    HIPCHK(hipGetLastError());
+    F.scale = f->noise_scale;
+  }
+  if (flags & DX_ACT_SMOOTH) F.alpha = f->smooth_alpha;
+  HIPCHK(hipStreamSynchronize(b->stream));
+  F.flags = flags;
+  return 0;
+}
+
+extern "C" int dx_env_action_noise_draw(dx_env* e, int32_t n, double* out_host) {
+  if (!e || !out_host) return fail(DX_EINVAL, "null argument");
+  if (!(e->F.flags & DX_ACT_NOISE)) return fail(DX_EINVAL, "action noise is not enabled");
+  if (n < 1 || n > DX_WAVE) return fail(DX_EINVAL, "between 1 and 64 normals per call");
+  dx_batch* b = e->batch;
+  HIPCHK(hipSetDevice(b->device));
+  double* dev = nullptr;
+  const size_t bytes = (size_t)e->P.nenv * n * 8;
+  HIPCHK(hipMalloc((void**)&dev, bytes));
+  hipLaunchKernelGGL(dx_action_noise_draw_kernel, dim3((e->P.nenv + DX_ACT_WAVES - 1) / DX_ACT_WAVES),
+                     dim3(DX_WAVE * DX_ACT_WAVES), 0, b->stream, e->P.nenv, (int)n, e->F.mt, dev);
+  hipError_t err = hipGetLastError();
+  if (err == hipSuccess) err = hipMemcpyAsync(out_host, dev, bytes, hipMemcpyDeviceToHost, b->stream);
+  if (err == hipSuccess) err = hipStreamSynchronize(b->stream);
+  (void)hipFree(dev);
+  if (err != hipSuccess) return fail(DX_EHIP, std::string("action noise draw: ") + hipGetErrorString(err));
+  return 0;
 }
 
 static int env_params_upload(dx_env* e) {
@@ -1981,6 +2088,13 @@ static std::vector<StateField> env_state_fields(dx_env* e) {
   if (S.mt_reach) f.push_back({"mt_reach", S.mt_reach, E * DX_MTW_WORDS * 4});
   if (B.cost) f.push_back({"step_cost", B.cost, E * 4});
   if (B.order) f.push_back({"order", (void*)B.order, E * 4});
+  if (e->F.flags) {  // the action pipeline's state, while it is enabled (its configuration is not saved)
+    const ActFilter& F = e->F;
+    f.push_back({"act_ema", F.ema, E * d.nu * 4});
+    f.push_back({"act_ema_set", F.ema_set, E * 4});
+    f.push_back({"prev_action", F.prev, E * d.nu * 4});
+    f.push_back({"mt_noise", F.mt, E * DX_MTW_WORDS * 4});
+  }
   return f;
 }
 
@@ -2045,6 +2159,10 @@ extern "C" int dx_env_output(dx_env* e, int which, void** devptr) {
     case DX_OUT_GOAL_QPOS:
       if (!e->S.goal_qpos) return fail(DX_EINVAL, "goal joints exist for the reach task only");
       *devptr = e->S.goal_qpos;
+      return 0;
+    case DX_OUT_PREV_ACTION:
+      if (!e->F.prev) return fail(DX_EINVAL, "no previous action: the action pipeline was never configured");
+      *devptr = e->F.prev;
       return 0;
   }
   return fail(DX_EINVAL, "unknown output");

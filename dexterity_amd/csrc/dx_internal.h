@@ -305,6 +305,24 @@ struct TaskState {
   int *nsub_d, *solve_n;
 };
 
+// The action pipeline ahead of the step (dx_env_set_action_filter; dx_task.hip
+// dx_action_filter_kernel): clipped Gaussian noise, the previous action, an exponential
+// moving average.  Its state belongs to the dx_env, not to TaskState: the step kernel
+// never sees it, it reads the filtered buffer `out` as its action.
+#define DX_ACT_WAVES 4   // envs (one wave each) per workgroup of the filter's kernels
+#define DX_ACT_NU_MAX 64 // one lane per actuator
+struct ActFilter {
+  int flags;            // DX_ACT_* (include/dx.h); 0: off
+  int nenv, nu;
+  float scale;           // noise stddev as a fraction of each actuator's ctrlrange
+  double alpha;          // EMA weight of the held value
+  const float* ctrlrange;              // the model's [nu][2]
+  const int *step_type, *episode;      // TaskState's, read before task_pre changes them
+  uint32_t* mt;          // the noise streams, [nenv][DX_MTW_WORDS] (RandomState(noise_seed + env0 + e))
+  float *ema, *prev, *out;             // [nenv][nu]
+  int* ema_set;          // [nenv]: the EMA holds a value (this episode)
+};
+
 // numpy.random.RandomState-compatible MT19937 ([3P] numpy legacy seeding and
 // random_sample: mt19937_seed, mt19937_gen, legacy_double), one stream per env kept in
 // HBM interleaved over the envs -- word k of env e at k * nenv + e (k < 624), the read

@@ -388,6 +388,8 @@ class GoalEnvironment:
         self._dev_action = self._out(-1)
         self._pins = []  # page-locked host buffers of step() (freed by close)
         self._pin_act = self._pin_out = None
+        # configure_actions' current arguments (the action pipeline is off by default)
+        self.action_config = dict(noise_scale=None, noise_seed=None, smooth_alpha=None, previous_action=False)
         if np.isfinite(self.time_limit):
             _lib.check(L.dx_env_set_time_limit(self.ptr, self.time_limit))
         # max_time_per_goal in fp64 (the params carry it as a float)
@@ -471,6 +473,41 @@ class GoalEnvironment:
         _lib.check(_lib.load().dx_env_sample_actions(self.ptr, self._seed, step))
         return self._dev_action
 
+    # ---------------------------------------------------------------- action pipeline
+    def configure_actions(self, noise_scale: Optional[float] = None, noise_seed: Optional[int] = None,
+                          smooth_alpha: Optional[float] = None, previous_action: bool = False) -> None:
+        """The reference's action-side wrappers on the device, ahead of every control step
+        (include/dx.h dx_env_set_action_filter; `dexterity_amd.wrappers` has their names):
+        `noise_scale` -- ActionNoise, clipped Gaussian noise of stddev noise_scale * (max -
+        min), env e drawing from RandomState(noise_seed + env_offset + e), `noise_seed`
+        defaulting to the env's seed; `smooth_alpha` -- SmoothAction's exponential moving
+        average; `previous_action` -- PreviousAction (kept whenever a stage is on).  All
+        None / False switches the pipeline off.  A checkpoint carries the pipeline's state
+        but not these settings: load it into an env configured the same way."""
+        f = _lib.ActionFilter()
+        if noise_scale is not None:
+            f.flags |= _lib.ACT_NOISE
+            f.noise_scale = float(noise_scale)
+            f.noise_seed = int(self._seed if noise_seed is None else noise_seed) & (2**64 - 1)
+        if smooth_alpha is not None:
+            f.flags |= _lib.ACT_SMOOTH
+            f.smooth_alpha = float(smooth_alpha)
+        if previous_action:
+            f.flags |= _lib.ACT_PREVIOUS
+        _lib.check(_lib.load().dx_env_set_action_filter(self.ptr, ctypes.byref(f)))
+        self.action_config = dict(noise_scale=noise_scale, noise_seed=noise_seed, smooth_alpha=smooth_alpha,
+                                  previous_action=bool(previous_action))
+
+    @property
+    def previous_action_ptr(self) -> int:
+        """Device address of the [num_envs, nu] float32 previous action."""
+        return self._out(_lib.OUT_PREV_ACTION)
+
+    def previous_action(self) -> np.ndarray:
+        """PreviousAction.previous_action of every env (host copy): the last command,
+        after the noise and before the smoothing; zeros at the start of an episode."""
+        return self._read(_lib.OUT_PREV_ACTION, np.float32, self.model.nu)
+
     # ---------------------------------------------------------------- checkpoint
     # dtype of the state fields that are not float32 (include/dx.h dx_env_save)
     _STATE_DTYPES = {"nstep": np.int32, "diverged": np.int32, "successes": np.int32, "counter": np.int32,
@@ -478,7 +515,8 @@ class GoalEnvironment:
                      "skip": np.int32, "failure": np.int32, "need": np.int32, "goalnum": np.int32,
                      "goalfail": np.int32, "time_d": np.float64, "solve_start_d": np.float64,
                      "nsub_d": np.int32, "solve_n": np.int32, "mt_env": np.uint32, "mt_goal": np.uint32,
-                     "mt_reach": np.uint32, "step_cost": np.uint32, "order": np.int32}
+                     "mt_reach": np.uint32, "step_cost": np.uint32, "order": np.int32,
+                     "act_ema_set": np.int32, "mt_noise": np.uint32}
 
     def _state_fields(self):
         L = _lib.load()
@@ -521,6 +559,12 @@ class GoalEnvironment:
             if "__agent_seed__" in z.files:
                 self._seed = int(z["__agent_seed__"][0])
             fields = self._state_fields()
+            # the action pipeline's state is in a checkpoint only while the pipeline is on,
+            # and its settings are not: the env must be configured as the saved one was
+            pipeline = {"act_ema", "act_ema_set", "prev_action", "mt_noise"}
+            if (pipeline <= set(z.files)) != (pipeline <= {name for name, _, _ in fields}):
+                raise ValueError("checkpoint and env differ in the action pipeline (on in one, off in the other): "
+                                 "configure_actions as the saved env was, then load")
             nbytes = sum(nb for _, _, nb in fields)
             buf = np.empty(nbytes, dtype=np.uint8)
             for name, off, nb in fields:
@@ -623,19 +667,26 @@ TASKS_BY_DOMAIN = {d: tuple(t for dd, t in ALL_TASKS if dd == d) for d in sorted
 
 def load(domain_name: str, task_name: str, seed: Optional[int] = None,
          strip_singleton_obs_buffer_dim: bool = True, time_limit: Optional[float] = None,
-         num_envs: int = 1, device: int = 0, env_offset: int = 0) -> GoalEnvironment:
+         num_envs: int = 1, device: int = 0, env_offset: int = 0, noise_scale: Optional[float] = None,
+         noise_seed: Optional[int] = None, smooth_alpha: Optional[float] = None,
+         previous_action: bool = False) -> GoalEnvironment:
     """manipulation/__init__.py:56-86, batched: the reference's arguments in its order,
     then the batch size and the GPU.  `time_limit=None` keeps the task's own limit
     (inf for every suite task).  Env e of the batch is the reference's environment
     loaded with seed `seed + env_offset + e`; `env_offset` places a shard of a sharded
-    job (distributed.env_shard) in the job's env numbering."""
+    job (distributed.env_shard) in the job's env numbering.  The last four arguments are
+    `GoalEnvironment.configure_actions`' (default: the action pipeline off)."""
     key = (domain_name, task_name)
     if domain_name not in {d for d, _ in SUITE}:
         raise ValueError(f"Unknown domain: {domain_name}")
     if key not in SUITE:
         raise ValueError(f"Unknown task: {task_name}")
-    return GoalEnvironment(SUITE[key](), num_envs=num_envs, seed=seed, device=device, time_limit=time_limit,
-                           strip_singleton_obs_buffer_dim=strip_singleton_obs_buffer_dim, env_offset=env_offset)
+    env = GoalEnvironment(SUITE[key](), num_envs=num_envs, seed=seed, device=device, time_limit=time_limit,
+                          strip_singleton_obs_buffer_dim=strip_singleton_obs_buffer_dim, env_offset=env_offset)
+    if noise_scale is not None or smooth_alpha is not None or previous_action:
+        env.configure_actions(noise_scale=noise_scale, noise_seed=noise_seed, smooth_alpha=smooth_alpha,
+                              previous_action=previous_action)
+    return env
 
 
 __all__ = ["load", "GoalEnvironment", "ReOrient", "ReOrientConfig", "Reach", "ReachConfig", "ALL_TASKS",

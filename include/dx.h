@@ -234,7 +234,9 @@ enum dx_task_kind { DX_TASK_REORIENT = 0, DX_TASK_REACH = 1, DX_TASK_HANDOVER = 
 enum dx_env_out { DX_OUT_OBS = 0, DX_OUT_REWARD = 1, DX_OUT_DISCOUNT = 2, DX_OUT_STEP_TYPE = 3,
                   DX_OUT_GOAL = 4, DX_OUT_SUCCESSES = 5, DX_OUT_GOAL_FAILURES = 6,
                   DX_OUT_GOAL_QPOS = 7 /* reach: [nenv][nq] f32, FingertipCartesianPosition.qpos
-                                          (fingertip_position.py:136-139) */ };
+                                          (fingertip_position.py:136-139) */,
+                  DX_OUT_PREV_ACTION = 8 /* [nenv][nu] f32, PreviousAction.previous_action; once the
+                                            action pipeline has been configured (below) */ };
 dx_env* dx_env_create(const dx_model* m, int32_t nenv, int32_t device, int32_t task, uint64_t seed,
                       const float* params, int32_t nparams);
 /* One shard of a job's environments: this handle's env e is the job's env env0 + e.
@@ -282,6 +284,45 @@ int dx_env_sample_actions(dx_env* e, uint64_t seed, int32_t step);
  * inside the step kernel (no action buffer, no extra launch): the random agent of the
  * reference's environment tests and of the benchmark. */
 int dx_env_step_random(dx_env* e, uint64_t seed, int32_t step);
+
+/* The action pipeline: the reference's three action-side wrappers on the device, one small
+ * kernel ahead of every control step (dx_env_step, dx_env_step_host, dx_env_step_random;
+ * the step then reads a library-owned filtered buffer, never the caller's).  Per env, in
+ * the order the reference nests them:
+ *  DX_ACT_NOISE     ActionNoise (manipulation/wrappers/action_noise.py): x = clip(a +
+ *    normal(scale = noise_scale * (max - min)), min, max) over the action spec's bounds,
+ *    the stddev in float32 as numpy computes it, the sum and the clip in fp64.  Drawn on
+ *    every step, also the one that re-initialises the env.  Env e draws from a stream of
+ *    its own, a numpy-compatible RandomState(noise_seed + env0 + e): replayable from numpy,
+ *    a shard equals the unsharded batch, and no other stream or checkpoint field moves (the
+ *    reference's wrapper shares the environment's RandomState: a stated deviation).
+ *  DX_ACT_PREVIOUS  PreviousAction (effectors/wrappers/previous_action.py), DX_OUT_PREV_ACTION:
+ *    the command of the last step, after the noise and before the smoothing; zeros at
+ *    initialize_episode (dx_env_reset, and the step that returns FIRST).  Kept whenever
+ *    the pipeline is on.
+ *  DX_ACT_SMOOTH    SmoothAction (effectors/wrappers/smooth_action.py): ctrl = alpha * held +
+ *    (1 - alpha) * x in fp64, restarted at initialize_episode (the first command of an
+ *    episode passes unchanged).
+ * dx_env_set_action_filter may be called between steps (it synchronises the stream);
+ * NULL or flags 0 switches the pipeline off, and the step's launches, the outputs and the
+ * checkpoint are then those of an env never configured.  DX_ACT_NOISE seeds (re-seeds) the
+ * noise stream.  DX_EINVAL: smooth_alpha outside [0, 1] or not finite, noise_scale negative
+ * or not finite, noise with an actuator that is not ctrllimited (an infinite stddev);
+ * DX_ELIMIT: more than 64 actuators.  dx_env_reset draws nothing.
+ * While the pipeline is on, the checkpoint (dx_env_save) carries its state after the
+ * other fields -- act_ema, act_ema_set (int32), prev_action, mt_noise -- but not this
+ * configuration: load a checkpoint into an env configured the same way. */
+enum { DX_ACT_NOISE = 1, DX_ACT_SMOOTH = 2, DX_ACT_PREVIOUS = 4 };
+typedef struct dx_action_filter {
+  int32_t flags;
+  float noise_scale;
+  double smooth_alpha;
+  uint64_t noise_seed;
+} dx_action_filter;
+int dx_env_set_action_filter(dx_env* e, const dx_action_filter* f);
+/* Test hook: the next n (1..64) standard normals of every env's noise stream, consumed;
+ * out_host [nenv][n] f64.  DX_ACT_NOISE must be on. */
+int dx_env_action_noise_draw(dx_env* e, int32_t n, double* out_host);
 
 /* Checkpoint / resume.  An env's state is the set of device arrays that carry from one
  * control step to the next (physics and task state, the numpy-compatible MT19937 streams,

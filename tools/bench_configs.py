@@ -4,7 +4,8 @@
 bench.py measures the headline (config 3); this script adds the other single-GPU
 configs, one JSON line each:
   config 2  reach_shadow.state_dense (contacts disabled), 1024 envs; also Adroit reach
-  config 3  reorient.state_dense, 4096 envs (same workload as bench.py)
+  config 3  reorient.state_dense, 4096 envs (same workload as bench.py); 3a: the same with the
+            action pipeline on (noise and EMA)
   config 5  bimanual handover physics (two Shadow hands + cube, nv 54), 4096 envs,
             random actions held for 5 physics substeps per control step
 Timed regions hold inputs in HBM (device-side actions), as in bench.py.
@@ -27,7 +28,7 @@ def _kernel_ms(L, ptr):
     return kt.value / max(1, kn.value), kn.value
 
 
-def env_config(name, domain, task, nenv, steps=50, warmup=10, solver=None):
+def env_config(name, domain, task, nenv, steps=50, warmup=10, solver=None, actions=None):
     from dexterity_amd import _lib, manipulation
 
     L = _lib.load()
@@ -37,6 +38,8 @@ def env_config(name, domain, task, nenv, steps=50, warmup=10, solver=None):
         t = manipulation.SUITE[(domain, task)]()
         t.compiled = t.compiled.with_solver(solver)
         env = manipulation.GoalEnvironment(t, num_envs=nenv, seed=7)
+    if actions:  # the action pipeline ahead of every step (GoalEnvironment.configure_actions)
+        env.configure_actions(**actions)
     env.reset()
     for i in range(warmup):
         env.step_random(i)
@@ -106,7 +109,7 @@ def bimanual(nenv=4096, steps=30, warmup=5, nsub=5):
 
 
 def main():
-    """Every config, or (arguments) only those whose key is given: 1 1' 2 2' 3 3' 3'' 5 5p."""
+    """Every config, or (arguments) only those whose key is given: 1 1' 2 2' 3 3a 3' 3'' 5 5p."""
     from bench import cpu_baseline_reach_1env
 
     runs = {
@@ -117,6 +120,9 @@ def main():
                                 steps=400, warmup=40),
         "2'": lambda: env_config("2' reach.state_dense (Adroit)", "reach", "state_dense", 1024, steps=200),
         "3": lambda: env_config("3 reorient.state_dense", "reorient", "state_dense", 4096),
+        # config 3 with ActionNoise + SmoothAction on the device: one more launch per control step
+        "3a": lambda: env_config("3a reorient.state_dense, action pipeline on (noise 0.05, EMA 0.7)", "reorient",
+                                 "state_dense", 4096, actions=dict(noise_scale=0.05, smooth_alpha=0.7)),
         "3'": lambda: env_config("3' reorient.state_dense, CG solver at MuJoCo's defaults", "reorient",
                                  "state_dense", 4096, solver="CG"),
         "3''": lambda: env_config("3'' reorient.state_dense, PGS solver at MuJoCo's defaults", "reorient",
