@@ -39,6 +39,7 @@ EXPORTS = (
     "dx_health", "dx_health_clear", "dx_ncon_histogram", "dx_env_set_goal_time_limit",
     "dx_env_step_random", "dx_env_save", "dx_env_load", "dx_env_state_field", "dx_env_step_host",
     "dx_build_key", "dx_env_set_action_filter", "dx_env_action_noise_draw",
+    "dx_env_set_hand_observables", "dx_env_hand_obs_dim",
 )
 COMM_ID_BYTES = 128
 STAGES = ("kinematics", "crb", "broadphase", "midphase", "narrowphase", "constraints", "velocity",
@@ -53,6 +54,9 @@ NP_STAGES = {36: "np_loop", 37: "np_fresh", 38: "np_supload", 39: "np_supred", 4
 OUT_OBS, OUT_REWARD, OUT_DISCOUNT, OUT_STEP_TYPE, OUT_GOAL, OUT_SUCCESSES, OUT_GOAL_FAILURES, OUT_GOAL_QPOS = range(8)
 OUT_PREV_ACTION = 8
 ACT_NOISE, ACT_SMOOTH, ACT_PREVIOUS = 1, 2, 4  # dx_action_filter.flags
+OUT_HAND_OBS = 9
+# dx_hand_obs.mask, in the order of the row's blocks within a hand
+HOBS_JOINT_POSITIONS, HOBS_TIP_ORIENTATIONS, HOBS_TIP_ANGULAR_VELOCITIES, HOBS_TIP_POSITIONS_EGO = 1, 2, 4, 8
 TASK_REORIENT, TASK_REACH, TASK_HANDOVER = 0, 1, 2
 REACH_NPARAMS_HEAD = 26
 
@@ -87,6 +91,16 @@ class ActionFilter(ctypes.Structure):
         ("noise_scale", ctypes.c_float),
         ("smooth_alpha", ctypes.c_double),
         ("noise_seed", ctypes.c_uint64),
+    ]
+
+
+class HandObs(ctypes.Structure):
+    """struct dx_hand_obs (include/dx.h)."""
+
+    _fields_ = [
+        ("mask", ctypes.c_int32),
+        ("nhands", ctypes.c_int32),
+        ("root_body", ctypes.c_int32 * 2),
     ]
 
 
@@ -171,6 +185,9 @@ def load(path: str = LIB_PATH):
     if hasattr(L, "dx_env_set_action_filter"):  # (an older variant library for A/B lacks the action pipeline)
         L.dx_env_set_action_filter.argtypes = [vp, ctypes.POINTER(ActionFilter)]
         L.dx_env_action_noise_draw.argtypes = [vp, i32, vp]
+    if hasattr(L, "dx_env_set_hand_observables"):  # (an older variant library for A/B lacks the hand observables)
+        L.dx_env_set_hand_observables.argtypes = [vp, ctypes.POINTER(HandObs)]
+        L.dx_env_hand_obs_dim.argtypes = [vp]
     L.dx_timing_enable.argtypes = [vp, ctypes.c_int]
     L.dx_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i32)]
     L.dx_stage_timing.argtypes = [vp, ctypes.c_int]

@@ -1680,6 +1680,12 @@ struct dx_env {
   // the action pipeline (dx_env_set_action_filter): off while F.flags == 0; its buffers
   // (F.mt != nullptr once allocated) are the batch's
   ActFilter F{};
+  // the optional hand observables (dx_env_set_hand_observables): off while H.mask == 0;
+  // the output and the fingertip tables are the batch's, sized for every observable of
+  // every fingertip at the first call; hobs_prev_bodies is the batch's body-pose setting
+  // from before orientations / ego positions switched it on (-1: not switched)
+  HandObs H{};
+  int hobs_prev_bodies = -1;
 };
 
 extern "C" dx_env* dx_env_create(const dx_model* m, int32_t nenv, int32_t device, int32_t task,
@@ -1854,6 +1860,18 @@ extern "C" int dx_env_obs_dim(const dx_env* e) { return e ? e->P.obs_dim : fail(
 extern "C" __global__ void dx_sample_actions_kernel(int nenv, int nu, const float* ctrlrange, uint64_t seed,
                                                     int step, int env0, float* out);
 
+// The optional hand observables' gather (dx_observe.hip), queued on the batch stream behind
+// a control step's last launch: launch_step has returned, so the overflow tier's launch --
+// where the mid tier's side stream is joined on the device -- or the order kernel of a
+// contact-free scene is ahead of it, and every tier's observation pass has written the
+// batch arrays it reads.  No stream event; nothing is launched while the feature is off.
+enum { HOBS_NEEDS_BODIES = DX_HOBS_TIP_ORIENTATIONS | DX_HOBS_TIP_POSITIONS_EGO };
+static int env_hand_obs(dx_env* e) {
+  if (!e->H.mask) return 0;
+  HIPCHK(dx_launch_hand_obs(e->batch->stream, e->H));
+  return 0;
+}
+
 // One control step.  The task logic runs fused into the step kernel (task_pre in each
 // env's first physics-step task, task_post in its last; dx_task.h): a reorient control step
 // is the step kernel plus the overflow tier's launch.  Reach (a reach scene's
@@ -1865,6 +1883,7 @@ extern "C" __global__ void dx_sample_actions_kernel(int nenv, int nu, const floa
 static int env_run(dx_env* e, const float* action, bool random = false, uint64_t seed = 0, int step = 0) {
   dx_batch* b = e->batch;
   HIPCHK(hipSetDevice(b->device));
+  if (e->H.mask & HOBS_NEEDS_BODIES) b->db.out_bodies = 1;  // (whatever dx_set_outputs was told since)
   if (e->F.flags && (action || random)) {
     // the action pipeline: one launch ahead of the step's, which then read the filtered
     // buffer (never the caller's); the random agent draws into the action buffer first --
@@ -1899,7 +1918,8 @@ static int env_run(dx_env* e, const float* action, bool random = false, uint64_t
     B.skip = skip;
     B.action = nullptr;
     B.act_random = 0;
-    return rc;
+    if (rc) return rc;
+    return env_hand_obs(e);
   }
   if (random) {  // the random agent into the action buffer, then the step
     void* buf = nullptr;
@@ -1920,7 +1940,7 @@ static int env_run(dx_env* e, const float* action, bool random = false, uint64_t
   if (int rc = launch_step(b, e->nsub, 0)) return rc;
   hipLaunchKernelGGL(dx_task_post_kernel, dim3((e->P.nenv + 3) / 4), dim3(256), 0, b->stream, e->P, e->S, b->db);  // a wave per env
   HIPCHK(hipGetLastError());
-  return 0;
+  return env_hand_obs(e);
 }
 
 extern "C" int dx_env_reset(dx_env* e) {
@@ -2016,6 +2036,134 @@ extern "C" int dx_env_action_noise_draw(dx_env* e, int32_t n, double* out_host) 
   return 0;
 }
 
+// ------------------------------------------------------------------------ //
+// the optional hand observables (dx_observe.hip dx_hand_obs_kernel)
+// ------------------------------------------------------------------------ //
+// Body poses of the env's CURRENT state into DX_XPOS / DX_XQUAT, for a batch that has been
+// stepping without them: the step kernel itself (the batch's own specialization, so the
+// poses are bit for bit those a step with body poses on would have left) launched over
+// every env as a just-reset one -- no physics step, only the observation pass -- on a
+// copy of the batch record whose every other output points at scratch memory.  The state
+// arrays it stores back (qpos, qvel, warm start, time, step count) get the values it
+// loaded.  Called with the stream drained; drains it again.
+static int env_refresh_body_poses(dx_env* e) {
+  dx_batch* b = e->batch;
+  const DevModel& d = b->dm;
+  const size_t E = b->nenv, ns = std::max(d.nsite, 1);
+  const size_t words[] = {E, E, E, E, E * d.nv, E * 3 * ns, E * 6 * ns};  // skip, ncon, niter, ncand, qacc, sites
+  size_t tot = 0;
+  for (size_t w : words) tot += w;
+  float* scratch = nullptr;
+  HIPCHK(hipMalloc((void**)&scratch, tot * 4));
+  std::vector<int> ones(E, 1);
+  hipError_t err = hipMemcpy(scratch, ones.data(), E * 4, hipMemcpyHostToDevice);
+  DevBatch B = b->db;
+  float* p = scratch;
+  B.skip = (const int*)p; p += words[0];
+  B.ncon = (int*)p; p += words[1];
+  B.niter = (int*)p; p += words[2];
+  B.ncand = (int*)p; p += words[3];
+  B.qacc = p; p += words[4];
+  B.site_xpos = p; p += words[5];
+  B.site_vel = p;
+  B.out_bodies = 1;
+  B.fuse = 0;
+  B.order = nullptr;  // workgroup k takes env k
+  B.cost = nullptr;
+  B.onext = 0;
+  B.bad = nullptr;    // (DX_DIVERGED keeps the last step's report)
+  B.watch = nullptr;
+  B.sen_stash = nullptr;
+  B.stage_acc = nullptr;
+  B.dbg_qacc_smooth = nullptr;
+  B.mid = 0;
+  if (err == hipSuccess)
+    err = dx_launch_step(b->spec, b->nenv, (size_t)b->model->lds.total * 4, b->stream, b->dm_dev, B, b->model->lds,
+                         e->nsub, 0);
+  if (err == hipSuccess) err = hipStreamSynchronize(b->stream);
+  (void)hipFree(scratch);
+  if (err != hipSuccess) return fail(DX_EHIP, std::string("hand observables: body poses: ") + hipGetErrorString(err));
+  return 0;
+}
+
+extern "C" int dx_env_set_hand_observables(dx_env* e, const dx_hand_obs* cfg) {
+  if (!e) return fail(DX_EINVAL, "null env");
+  dx_batch* b = e->batch;
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));  // may be called between steps
+  const int mask = cfg ? cfg->mask : 0;
+  const int all = DX_HOBS_JOINT_POSITIONS | DX_HOBS_TIP_ORIENTATIONS | DX_HOBS_TIP_ANGULAR_VELOCITIES |
+                  DX_HOBS_TIP_POSITIONS_EGO;
+  if (mask & ~all) return fail(DX_EINVAL, "hand observables: unknown bit in the mask");
+  HandObs& H = e->H;
+  const TaskParams& P = e->P;
+  const DevModel& d = b->dm;
+  if (!mask) {  // off: a control step launches what an env never configured launches
+    H.mask = 0;
+    if (e->hobs_prev_bodies >= 0) b->db.out_bodies = e->hobs_prev_bodies;
+    e->hobs_prev_bodies = -1;
+    return 0;
+  }
+  const int nhands = P.kind == DX_KIND_HANDOVER ? 2 : 1;
+  if (cfg->nhands != nhands) return fail(DX_EINVAL, "hand observables: nhands differs from the task's hand count");
+  for (int h = 0; h < nhands; h++)
+    if (cfg->root_body[h] < 0 || cfg->root_body[h] >= d.nbody)
+      return fail(DX_EINVAL, "hand observables: root body outside [0, nbody)");
+  if (P.hand_nq % nhands || P.ntips % nhands) return fail(DX_EINVAL, "hand observables: the hands differ in size");
+  const int hnq = P.hand_nq / nhands, nt = P.ntips / nhands;
+  const int hand_dim = ((mask & DX_HOBS_JOINT_POSITIONS) ? hnq : 0) + ((mask & DX_HOBS_TIP_ORIENTATIONS) ? 4 * nt : 0) +
+                       ((mask & DX_HOBS_TIP_ANGULAR_VELOCITIES) ? 3 * nt : 0) +
+                       ((mask & DX_HOBS_TIP_POSITIONS_EGO) ? 3 * nt : 0);
+  if (hand_dim < 1) return fail(DX_EINVAL, "hand observables: the task has nothing of what the mask names");
+  const int full = nhands * (hnq + 10 * nt);  // every observable on
+  if ((size_t)P.nenv * full >= 0x7fffffffull) return fail(DX_ELIMIT, "hand observables: nenv * width above 2^31");
+  if (!H.out) {  // first use: the buffer at its full width, the task's fingertip sites and their site_quat
+    HandObs A{};
+    const auto& sq = b->model->hf.at("site_quat");
+    std::vector<float> tq(4 * std::max(P.ntips, 1), 0.f);
+    for (int t = 0; t < P.ntips; t++)
+      for (int k = 0; k < 4; k++) tq[4 * t + k] = sq[4 * P.tip_sites[t] + k];
+    int rc = balloc(b, (void**)&A.out, (size_t)P.nenv * full * 4);
+    if (!rc) rc = balloc(b, (void**)&A.tip_site, (size_t)std::max(P.ntips, 1) * 4);
+    if (!rc) rc = balloc(b, (void**)&A.tip_quat, tq.size() * 4);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(b->stream));  // balloc zeroes on the stream: ahead of the copies
+    HIPCHK(hipMemcpy((void*)A.tip_site, P.tip_sites, (size_t)P.ntips * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy((void*)A.tip_quat, tq.data(), tq.size() * 4, hipMemcpyHostToDevice));
+    const DevBatch& B = b->db;
+    A.nenv = P.nenv; A.nq = d.nq; A.nsite = d.nsite; A.nbody = d.nbody;
+    A.nhands = nhands; A.hand_nq = hnq; A.ntips = nt;
+    A.qpos = B.qpos; A.site_xpos = B.site_xpos; A.site_vel = B.site_vel; A.xpos = B.xpos; A.xquat = B.xquat;
+    A.site_bodyid = (const int*)d.site_bodyid;
+    A.body_ipos = (const float*)d.body_ipos;
+    A.body_imat = (const float*)d.body_imat;
+    H = A;
+  }
+  // body poses of the current state, when the batch has been stepping without them
+  if ((mask & HOBS_NEEDS_BODIES) && !b->db.out_bodies)
+    if (int rc = env_refresh_body_poses(e)) return rc;
+  if (mask & HOBS_NEEDS_BODIES) {
+    if (e->hobs_prev_bodies < 0) e->hobs_prev_bodies = b->db.out_bodies;
+    b->db.out_bodies = 1;
+  } else if (e->hobs_prev_bodies >= 0) {
+    b->db.out_bodies = e->hobs_prev_bodies;
+    e->hobs_prev_bodies = -1;
+  }
+  for (int h = 0; h < nhands; h++) H.root[h] = cfg->root_body[h];
+  H.hand_dim = hand_dim;
+  H.dim = nhands * hand_dim;
+  H.mask = mask;
+  // the output holds the current state's values from here on (enabling mid-episode)
+  if (int rc = env_hand_obs(e)) return rc;
+  HIPCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+extern "C" int dx_env_hand_obs_dim(const dx_env* e) {
+  if (!e) return fail(DX_EINVAL, "null env");
+  return e->H.mask ? e->H.dim : 0;
+}
+
 static int env_params_upload(dx_env* e) {
   HIPCHK(hipSetDevice(e->batch->device));
   HIPCHK(hipStreamSynchronize(e->batch->stream));  // the device copy is read by the sampling pass
@@ -2095,6 +2243,9 @@ static std::vector<StateField> env_state_fields(dx_env* e) {
     f.push_back({"prev_action", F.prev, E * d.nu * 4});
     f.push_back({"mt_noise", F.mt, E * DX_MTW_WORDS * 4});
   }
+  // the hand observables' rows, while they are on (their configuration is not saved): a
+  // loaded env reads what the saved one would have, before its next step rewrites them
+  if (e->H.mask) f.push_back({"hand_obs", e->H.out, E * e->H.dim * 4});
   return f;
 }
 
@@ -2163,6 +2314,10 @@ extern "C" int dx_env_output(dx_env* e, int which, void** devptr) {
     case DX_OUT_PREV_ACTION:
       if (!e->F.prev) return fail(DX_EINVAL, "no previous action: the action pipeline was never configured");
       *devptr = e->F.prev;
+      return 0;
+    case DX_OUT_HAND_OBS:
+      if (!e->H.mask) return fail(DX_EINVAL, "no hand observables: dx_env_set_hand_observables has none enabled");
+      *devptr = e->H.out;
       return 0;
   }
   return fail(DX_EINVAL, "unknown output");

@@ -323,6 +323,27 @@ struct ActFilter {
   int* ema_set;          // [nenv]: the EMA holds a value (this episode)
 };
 
+// The optional hand observables behind the step (dx_env_set_hand_observables;
+// dx_observe.hip dx_hand_obs_kernel): a gather over what the step's observation pass left
+// in the batch arrays.  Like the action pipeline's, its state belongs to the dx_env: the
+// step kernel never sees it.  Row layout of `out`: hand 0 | hand 1, and within a hand the
+// enabled observables in the order of the DX_HOBS_* bits.
+#define DX_HOBS_MAX_HANDS 2
+#define DX_HOBS_THREADS 256  // output elements (one lane each) per workgroup
+struct HandObs {
+  int mask;                      // DX_HOBS_* (include/dx.h); 0: off
+  int nenv, nq, nsite, nbody;
+  int nhands, hand_nq, ntips;    // hand h: qpos[h * hand_nq ...], fingertips h * ntips ...
+  int hand_dim, dim;             // floats per hand, per env (nhands * hand_dim)
+  int root[DX_HOBS_MAX_HANDS];   // the hand's root body (fingertip_positions_ego)
+  const float *qpos, *site_xpos, *site_vel, *xpos, *xquat;  // the batch's
+  const int* site_bodyid;        // the model's
+  const float *body_ipos, *body_imat;
+  const int* tip_site;           // [nhands * ntips] the task's fingertip sites
+  const float* tip_quat;         // [nhands * ntips][4] the model's site_quat of each
+  float* out;                    // [nenv][dim]
+};
+
 // numpy.random.RandomState-compatible MT19937 ([3P] numpy legacy seeding and
 // random_sample: mt19937_seed, mt19937_gen, legacy_double), one stream per env kept in
 // HBM interleaved over the envs -- word k of env e at k * nenv + e (k < 624), the read
@@ -457,3 +478,6 @@ hipError_t dx_launch_ik(int nwave, size_t lds, hipStream_t stream, const DevMode
                         const Lds& L, const IkDev& P);
 hipError_t dx_launch_ik_select(int nenv, hipStream_t stream, const DevModel& m, const IkDev& P, float* qpos_out,
                                int* success, float* err_out, int* attempt_out, int* steps_out);
+
+// dx_observe.hip: the optional hand observables' gather, queued behind the step's launches
+hipError_t dx_launch_hand_obs(hipStream_t stream, const HandObs& H);

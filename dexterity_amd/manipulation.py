@@ -64,6 +64,19 @@ class ReOrientConfig:
         return self.max_steps_single_solve * self.control_timestep
 
 
+# The optional hand observables (GoalEnvironment.enable_observables; include/dx.h
+# dx_env_set_hand_observables), in the reference's declaration order
+# (dexterous_hand.py:245-372) -- the order of a hand's blocks in a DX_OUT_HAND_OBS row:
+# name -> (mask bit, floats per joint, floats per fingertip)
+HAND_EXTRA_OBSERVABLES = collections.OrderedDict((
+    ("joint_positions", (_lib.HOBS_JOINT_POSITIONS, 1, 0)),
+    ("fingertip_orientations", (_lib.HOBS_TIP_ORIENTATIONS, 0, 4)),
+    ("fingertip_angular_velocities", (_lib.HOBS_TIP_ANGULAR_VELOCITIES, 0, 3)),
+    ("fingertip_positions_ego", (_lib.HOBS_TIP_POSITIONS_EGO, 0, 3)),
+))
+HAND_ROOT_BODY = "forearm"  # hand.root_body: shadow_hand_e.py:62, adroit_hand.py:57
+
+
 def observation_layout(hand_nq: int, hand_nv: int, ntips: int, with_prop: bool, hand: str,
                        goal_dim: int = 4) -> "collections.OrderedDict[str, slice]":
     """Named slices of the flat observation vector written by dx_task_post_kernel."""
@@ -102,6 +115,7 @@ class ReOrient:
         if abs(cm.timestep - config.physics_timestep) > 1e-12:
             raise ValueError("asset timestep does not match the task's physics timestep")
         self.hand_name = "shadow_hand_e"
+        self.hand_names = (self.hand_name,)
         names = cm.names
         self.hand_joint_ids = [i for i, n in enumerate(names["joint"]) if n.startswith(self.hand_name + "/")]
         self.hand_nq = len(self.hand_joint_ids)
@@ -307,6 +321,7 @@ class Reach:
             tips = [f"{self.hand_name}/{t}_site" for t in hands_lib.SHADOW_FINGERTIPS]
             self.position_to_control = hands_lib.POSITION_TO_CONTROL  # shadow_hand_e.py:109-119
             coupled = [(ids[0], ids[-1]) for ids in hands_lib.COUPLED_JOINT_IDS]  # shadow_hand_e.py:124-129
+        self.hand_names = (self.hand_name,)
         self.tip_sites = [names["site"].index(t) for t in tips]
         self.coupled = coupled
         self.hand_nq = cm.nq
@@ -390,6 +405,10 @@ class GoalEnvironment:
         self._pin_act = self._pin_out = None
         # configure_actions' current arguments (the action pipeline is off by default)
         self.action_config = dict(noise_scale=None, noise_seed=None, smooth_alpha=None, previous_action=False)
+        # enable_observables' current names, the row width and the named slices of a row
+        self.hand_observables = ()
+        self.hand_obs_dim = 0
+        self._hand_layout = collections.OrderedDict()
         if np.isfinite(self.time_limit):
             _lib.check(L.dx_env_set_time_limit(self.ptr, self.time_limit))
         # max_time_per_goal in fp64 (the params carry it as a float)
@@ -425,13 +444,24 @@ class GoalEnvironment:
     def observation_spec(self) -> "collections.OrderedDict[str, Array]":
         lead = () if self.strip_singleton_obs_buffer_dim else (1,)
         return collections.OrderedDict(
-            (k, Array(lead + (s.stop - s.start,), np.float64, name=k)) for k, s in self._layout.items()
+            (k, Array(lead + (s.stop - s.start,), np.float64, name=k))
+            for k, s in list(self._layout.items()) + list(self._hand_layout.items())
         )
 
     # ---------------------------------------------------------------- stepping
     def reset(self) -> TimeStep:
         _lib.check(_lib.load().dx_env_reset(self.ptr))
         return self.timestep(first=True)
+
+    def _hand_observation(self) -> "collections.OrderedDict[str, np.ndarray]":
+        """The enabled optional hand observables (one device-to-host copy of
+        DX_OUT_HAND_OBS); empty, and no copy, while none is enabled."""
+        out = collections.OrderedDict()
+        if self.hand_obs_dim:
+            rows = self.hand_obs()
+            for k, s in self._hand_layout.items():
+                out[k] = (rows[:, s] if self.strip_singleton_obs_buffer_dim else rows[:, None, s]).astype(np.float64)
+        return out
 
     def step(self, action, device_action: bool = False) -> Optional[TimeStep]:
         L = _lib.load()
@@ -451,7 +481,10 @@ class GoalEnvironment:
             self._pin_out = _pinned((self.num_envs, self.obs_dim + 3), np.float32, self._pins)
         np.copyto(self._pin_act, a)
         _lib.check(L.dx_env_step_host(self.ptr, self._pin_act.ctypes.data, self._pin_out.ctypes.data))
-        return self._timestep_packed(self._pin_out)
+        ts = self._timestep_packed(self._pin_out)
+        if self.hand_obs_dim:  # the packed row does not carry them: one more copy
+            ts.observation.update(self._hand_observation())
+        return ts
 
     def _timestep_packed(self, packed: np.ndarray) -> TimeStep:
         """A TimeStep (copies) from the packed [obs | reward | discount | step_type] rows."""
@@ -507,6 +540,55 @@ class GoalEnvironment:
         """PreviousAction.previous_action of every env (host copy): the last command,
         after the noise and before the smoothing; zeros at the start of an episode."""
         return self._read(_lib.OUT_PREV_ACTION, np.float32, self.model.nu)
+
+    # ---------------------------------------------------------------- hand observables
+    def enable_observables(self, names) -> None:
+        """The reference's `hand.observables.<name>.enabled = True` for the observables the
+        fixed observation does not carry (HAND_EXTRA_OBSERVABLES: joint_positions,
+        fingertip_orientations, fingertip_angular_velocities, fingertip_positions_ego),
+        computed on the device behind every control step (include/dx.h
+        dx_env_set_hand_observables).  `names` is the whole set to have on; an empty one
+        switches the feature off.  They arrive as `f"{hand}/{name}"` after the existing
+        keys of `observation_spec()` and of every TimeStep, and describe the same state
+        as the rest of the observation -- also right after this call, before or after
+        `reset`.  A checkpoint carries their values but not this setting."""
+        names = [names] if isinstance(names, str) else list(names)
+        unknown = [n for n in names if n not in HAND_EXTRA_OBSERVABLES]
+        if unknown:
+            raise ValueError(f"unknown hand observables {unknown}; the optional ones are "
+                             f"{list(HAND_EXTRA_OBSERVABLES)}")
+        L = _lib.load()
+        hands = self.task.hand_names
+        cfg = _lib.HandObs()
+        cfg.nhands = len(hands)
+        for name in names:
+            cfg.mask |= HAND_EXTRA_OBSERVABLES[name][0]
+        bodies = self.task.compiled.names["body"]
+        for h, hand in enumerate(hands):
+            cfg.root_body[h] = bodies.index(f"{hand}/{HAND_ROOT_BODY}")
+        _lib.check(L.dx_env_set_hand_observables(self.ptr, ctypes.byref(cfg)))
+        enabled = tuple(n for n in HAND_EXTRA_OBSERVABLES if n in names)
+        nq, nt = self.task.hand_nq // len(hands), self.task.ntips // len(hands)
+        layout, k = collections.OrderedDict(), 0
+        for hand in hands:
+            for n in enabled:
+                _, per_joint, per_tip = HAND_EXTRA_OBSERVABLES[n]
+                w = per_joint * nq + per_tip * nt
+                layout[f"{hand}/{n}"] = slice(k, k + w)
+                k += w
+        self.hand_obs_dim = _lib.check(L.dx_env_hand_obs_dim(self.ptr))
+        assert self.hand_obs_dim == k, (self.hand_obs_dim, k)
+        self.hand_observables = enabled
+        self._hand_layout = layout
+
+    @property
+    def hand_obs_ptr(self) -> int:
+        """Device address of the [num_envs, hand_obs_dim] float32 rows (while enabled)."""
+        return self._out(_lib.OUT_HAND_OBS)
+
+    def hand_obs(self) -> np.ndarray:
+        """[num_envs, hand_obs_dim] float32 host copy of the rows (DxError while off)."""
+        return self._read(_lib.OUT_HAND_OBS, np.float32, self.hand_obs_dim)
 
     # ---------------------------------------------------------------- checkpoint
     # dtype of the state fields that are not float32 (include/dx.h dx_env_save)
@@ -565,6 +647,9 @@ class GoalEnvironment:
             if (pipeline <= set(z.files)) != (pipeline <= {name for name, _, _ in fields}):
                 raise ValueError("checkpoint and env differ in the action pipeline (on in one, off in the other): "
                                  "configure_actions as the saved env was, then load")
+            if ("hand_obs" in z.files) != ("hand_obs" in {name for name, _, _ in fields}):
+                raise ValueError("checkpoint and env differ in the hand observables (on in one, off in the other): "
+                                 "enable_observables as the saved env did, then load")
             nbytes = sum(nb for _, _, nb in fields)
             buf = np.empty(nbytes, dtype=np.uint8)
             for name, off, nb in fields:
@@ -593,6 +678,7 @@ class GoalEnvironment:
             (k, obs[:, s].astype(np.float64) if self.strip_singleton_obs_buffer_dim
              else obs[:, None, s].astype(np.float64)) for k, s in self._layout.items()
         )
+        observation.update(self._hand_observation())
         return TimeStep(st.astype(np.int32), rew, disc, observation)
 
     def goals(self) -> np.ndarray:
@@ -690,4 +776,4 @@ def load(domain_name: str, task_name: str, seed: Optional[int] = None,
 
 
 __all__ = ["load", "GoalEnvironment", "ReOrient", "ReOrientConfig", "Reach", "ReachConfig", "ALL_TASKS",
-           "ALL_NAMES", "TASKS_BY_DOMAIN", "StepType"]
+           "ALL_NAMES", "TASKS_BY_DOMAIN", "StepType", "HAND_EXTRA_OBSERVABLES"]

@@ -236,7 +236,9 @@ enum dx_env_out { DX_OUT_OBS = 0, DX_OUT_REWARD = 1, DX_OUT_DISCOUNT = 2, DX_OUT
                   DX_OUT_GOAL_QPOS = 7 /* reach: [nenv][nq] f32, FingertipCartesianPosition.qpos
                                           (fingertip_position.py:136-139) */,
                   DX_OUT_PREV_ACTION = 8 /* [nenv][nu] f32, PreviousAction.previous_action; once the
-                                            action pipeline has been configured (below) */ };
+                                            action pipeline has been configured (below) */,
+                  DX_OUT_HAND_OBS = 9 /* [nenv][dx_env_hand_obs_dim] f32, the optional hand
+                                         observables; while they are on (below) */ };
 dx_env* dx_env_create(const dx_model* m, int32_t nenv, int32_t device, int32_t task, uint64_t seed,
                       const float* params, int32_t nparams);
 /* One shard of a job's environments: this handle's env e is the job's env env0 + e.
@@ -323,6 +325,47 @@ int dx_env_set_action_filter(dx_env* e, const dx_action_filter* f);
 /* Test hook: the next n (1..64) standard normals of every env's noise stream, consumed;
  * out_host [nenv][n] f64.  DX_ACT_NOISE must be on. */
 int dx_env_action_noise_draw(dx_env* e, int32_t n, double* out_host);
+
+/* The optional hand observables: those of the reference's hand entity
+ * (models/hands/dexterous_hand.py:245-372) that the fixed observation does not carry, as
+ * one small gather kernel behind every call that produces DX_OUT_OBS (dx_env_reset,
+ * dx_env_step, dx_env_step_random, dx_env_step_host); its values describe the same state
+ * as that observation, also on the FIRST step of an auto-reset env.  Per hand, in the
+ * reference's declaration order (hand_nq joints and ntips fingertips PER HAND):
+ *  DX_HOBS_JOINT_POSITIONS         hand_nq    qpos at the hand's joints (bit-equal to DX_QPOS)
+ *  DX_HOBS_TIP_ORIENTATIONS        4 ntips    unit quaternion (w, x, y, z) of each fingertip
+ *    site's xmat, canonical with w >= 0 ([3P] dm_robotics mat_to_quat's sign): normalised
+ *    xquat[site_bodyid] (x) site_quat, negated when w < 0
+ *  DX_HOBS_TIP_ANGULAR_VELOCITIES  3 ntips    world-frame angular velocity at each fingertip
+ *    site (mj_objectVelocity, utils/mujoco_utils.py:10-35; bit-equal to DX_SITE_VEL words 3-5)
+ *  DX_HOBS_TIP_POSITIONS_EGO       3 ntips    each fingertip site in the hand's root body's
+ *    INERTIAL frame ([3P] framepos with reftype="body"): ximat^T (site_xpos - xipos)
+ * DX_OUT_HAND_OBS is a library-owned [nenv][dx_env_hand_obs_dim] f32 buffer: hands in the
+ * task's order (handover: left, then right; nhands = 2, else 1), within a hand the
+ * enabled observables in the order above.  An element's value does not depend on the
+ * mask.  The fingertip sites are the task's (the ones `fingertip_positions` uses).
+ * dx_env_set_hand_observables may be called between steps (it synchronises the stream)
+ * and, with a non-zero mask, leaves the buffer holding the env's current state: enabling
+ * mid-episode equals enabling before dx_env_reset.  While orientations or ego positions
+ * are on, the env's batch writes body poses (dx_set_outputs(batch, 1); the setting from
+ * before is restored when the feature goes off).  NULL or mask 0 switches the feature off
+ * (the default): a control step then launches what it launched before, and
+ * dx_env_output(DX_OUT_HAND_OBS) fails.  DX_EINVAL (configuration unchanged): an unknown
+ * bit, a root body outside [0, nbody), nhands other than the task's.  While the feature
+ * is on, the checkpoint carries the buffer as its last field, hand_obs, but not this
+ * configuration.  DX_OUT_OBS, dx_env_obs_dim and the packed rows are never affected.
+ * joint_torques stays at the physics level (DX_SENSOR_TORQUE): a freshly reset env is only
+ * observed, so the env step has no solved forces for it. */
+enum { DX_HOBS_JOINT_POSITIONS = 1, DX_HOBS_TIP_ORIENTATIONS = 2, DX_HOBS_TIP_ANGULAR_VELOCITIES = 4,
+       DX_HOBS_TIP_POSITIONS_EGO = 8 };
+typedef struct dx_hand_obs {
+  int32_t mask;          /* DX_HOBS_* */
+  int32_t nhands;        /* the task's hand count */
+  int32_t root_body[2];  /* one root body id per hand (the reference's hand.root_body) */
+} dx_hand_obs;
+int dx_env_set_hand_observables(dx_env* e, const dx_hand_obs* cfg);
+/* Row width of DX_OUT_HAND_OBS; 0 while the feature is off. */
+int dx_env_hand_obs_dim(const dx_env* e);
 
 /* Checkpoint / resume.  An env's state is the set of device arrays that carry from one
  * control step to the next (physics and task state, the numpy-compatible MT19937 streams,
