@@ -32,7 +32,7 @@ EXPORTS = (
     "dx_env_step", "dx_env_output", "dx_env_action_buffer", "dx_env_sample_actions",
     "dx_env_pack_outputs", "dx_timing_enable", "dx_timing_read", "dx_stage_timing", "dx_stage_read",
     "dx_debug_poison_lds", "dx_hull_support", "dx_model_layout", "dx_env_goal_dim",
-    "dx_jac_site", "dx_ik_solve",
+    "dx_jac_site", "dx_ik_solve", "dx_jac_object", "dx_dls_map",
     "dx_comm_unique_id", "dx_comm_init", "dx_comm_destroy", "dx_comm_rank", "dx_comm_size",
     "dx_allgather_obs", "dx_comm_allreduce_max", "dx_comm_barrier", "dx_sensor_enable",
     "dx_env_set_time_limit", "dx_set_outputs", "dx_env_create_shard",
@@ -58,6 +58,7 @@ OUT_HAND_OBS = 9
 # dx_hand_obs.mask, in the order of the row's blocks within a hand
 HOBS_JOINT_POSITIONS, HOBS_TIP_ORIENTATIONS, HOBS_TIP_ANGULAR_VELOCITIES, HOBS_TIP_POSITIONS_EGO = 1, 2, 4, 8
 TASK_REORIENT, TASK_REACH, TASK_HANDOVER = 0, 1, 2
+OBJ_BODY, OBJ_GEOM, OBJ_SITE = 1, 5, 6  # dx_obj_type (MuJoCo's mjtObj values)
 REACH_NPARAMS_HEAD = 26
 
 _lib = None
@@ -195,6 +196,9 @@ def load(path: str = LIB_PATH):
     L.dx_debug_poison_lds.argtypes = [i32]
     L.dx_jac_site.argtypes = [vp, vp, i32, vp, vp]
     L.dx_ik_solve.argtypes = [vp, ctypes.POINTER(IkOptions), vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "dx_dls_map"):  # (an older variant library for A/B lacks the velocity mapper)
+        L.dx_jac_object.argtypes = [vp, vp, vp, i32, vp, vp]
+        L.dx_dls_map.argtypes = [vp, vp, vp, i32, ctypes.c_float, vp, vp, vp]
     L.dx_comm_unique_id.argtypes = [vp]
     L.dx_comm_init.restype = vp
     L.dx_comm_init.argtypes = [ctypes.c_char_p, i32, i32, i32]

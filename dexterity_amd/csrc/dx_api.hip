@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <array>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -1550,6 +1551,127 @@ extern "C" int dx_ik_solve(dx_batch* b, const dx_ik_options* opt, const int32_t*
   if (attempt) HIPCHK(hipMemcpyAsync(attempt, oa, E * 4, hipMemcpyDefault, b->stream));
   if (steps) HIPCHK(hipMemcpyAsync(steps, ot, E * 4, hipMemcpyDefault, b->stream));
   HIPCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+// dx_jac_object / dx_dls_map: the controlled objects as points (dx_internal.h DlsDev).
+// Every argument error returns here, before any launch.
+static int dls_points(dx_batch* b, const int32_t* types, const int32_t* ids, int32_t nobj, DlsDev& P) {
+  if (!b) return fail(DX_EINVAL, "null batch");
+  if (!types || !ids || nobj < 1) return fail(DX_EINVAL, "need nobj >= 1 object types and ids");
+  const dx_model* m = b->model;
+  memset(&P, 0, sizeof(P));
+  for (int k = 0; k < nobj; k++) {
+    const int t = types[k], id = ids[k];
+    const int n = t == DX_OBJ_BODY ? b->dm.nbody : t == DX_OBJ_GEOM ? b->dm.ngeom : t == DX_OBJ_SITE ? b->dm.nsite : -1;
+    if (n < 0) return fail(DX_EINVAL, "object type must be DX_OBJ_BODY, DX_OBJ_GEOM or DX_OBJ_SITE");
+    if (id < 0 || id >= n) return fail(DX_EINVAL, "object id out of range");
+    if (k >= DX_DLS_MAXPT) continue;  // (DX_ELIMIT below, after every object was validated)
+    const float* off = nullptr;
+    int body = id;
+    if (t == DX_OBJ_GEOM) {
+      body = m->hi.at("geom_bodyid")[id];
+      off = m->hf.at("geom_pos").data() + 3 * id;
+    } else if (t == DX_OBJ_SITE) {
+      body = m->hi.at("site_bodyid")[id];
+      off = m->hf.at("site_pos").data() + 3 * id;
+    }
+    P.body[k] = body;
+    for (int e = 0; e < 3; e++) P.off[3 * k + e] = off ? off[e] : 0.f;
+  }
+  if (3 * nobj > 32) return fail(DX_ELIMIT, "3 * nobj must be <= 32 (one 32 x 32 matrix-core tile)");
+  if (b->dm.nv > DX_MAX_NV) return fail(DX_ELIMIT, "nv must be <= 64");
+  P.npoint = nobj;
+  P.blk = m->lds.total;
+  return 0;
+}
+
+static int dls_lds_bytes(dx_batch* b, size_t* bytes) {
+  *bytes = ((size_t)b->model->lds.total + dx_dls_lds_words(b->dm)) * 4;
+  if (*bytes > 160 * 1024) return fail(DX_ELIMIT, "mapper LDS footprint exceeds 160 KiB");
+  return 0;
+}
+
+// Host or device memory?  (An address HIP does not know is ordinary host memory.)
+static bool is_device_ptr(const void* p) {
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return a.type == hipMemoryTypeDevice;
+}
+
+// One argument array of a mapper call: device memory is used in place; host memory is
+// staged through device scratch (copied in before the launch, or out after it).
+struct DlsArg {
+  void* user = nullptr;
+  void* dev = nullptr;
+  size_t bytes = 0;
+  bool staged = false;
+};
+static bool dls_arg(DlsArg& a, const void* user, size_t bytes, std::unique_ptr<CallScratch>& S, hipStream_t stream) {
+  a.user = (void*)user;
+  a.bytes = bytes;
+  if (!user) return true;
+  if (is_device_ptr(user)) {
+    a.dev = a.user;
+    return true;
+  }
+  if (!S) S.reset(new CallScratch(stream));
+  a.dev = S->get(bytes);
+  a.staged = true;
+  return a.dev != nullptr;
+}
+
+extern "C" int dx_jac_object(dx_batch* b, const int32_t* types, const int32_t* ids, int32_t nobj, float* jacp,
+                             float* jacr) {
+  DlsDev P;
+  if (int rc = dls_points(b, types, ids, nobj, P)) return rc;
+  size_t lds;
+  if (int rc = dls_lds_bytes(b, &lds)) return rc;
+  HIPCHK(hipSetDevice(b->device));
+  const size_t n = (size_t)b->nenv * 3 * nobj * b->dm.nv * 4;
+  std::unique_ptr<CallScratch> S;  // (synchronises the stream when it goes)
+  DlsArg ap, ar;
+  if (!dls_arg(ap, jacp, n, S, b->stream) || !dls_arg(ar, jacr, n, S, b->stream))
+    return fail(DX_ENOMEM, "device scratch allocation failed");
+  P.mode = 1;
+  P.jacp = (float*)ap.dev;
+  P.jacr = (float*)ar.dev;
+  HIPCHK(dx_launch_dls(b->nenv, lds, b->stream, b->dm_dev, b->db, b->model->lds, P));
+  if (ap.staged) HIPCHK(hipMemcpyAsync(ap.user, ap.dev, n, hipMemcpyDeviceToHost, b->stream));
+  if (ar.staged) HIPCHK(hipMemcpyAsync(ar.user, ar.dev, n, hipMemcpyDeviceToHost, b->stream));
+  if (S) HIPCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+extern "C" int dx_dls_map(dx_batch* b, const int32_t* types, const int32_t* ids, int32_t nobj, float regularization,
+                          const float* target_vel, float* qvel_out, int32_t* status) {
+  DlsDev P;
+  if (int rc = dls_points(b, types, ids, nobj, P)) return rc;
+  if (!(regularization >= 0.f) || std::isinf(regularization))
+    return fail(DX_EINVAL, "regularization must be finite and non-negative");
+  if (!target_vel || !qvel_out) return fail(DX_EINVAL, "null target_vel or qvel_out");
+  size_t lds;
+  if (int rc = dls_lds_bytes(b, &lds)) return rc;
+  HIPCHK(hipSetDevice(b->device));
+  const size_t E = b->nenv;
+  std::unique_ptr<CallScratch> S;  // (synchronises the stream when it goes)
+  DlsArg at, aq, as;
+  if (!dls_arg(at, target_vel, E * 3 * nobj * 4, S, b->stream) || !dls_arg(aq, qvel_out, E * b->dm.nv * 4, S, b->stream) ||
+      !dls_arg(as, status, E * 4, S, b->stream))
+    return fail(DX_ENOMEM, "device scratch allocation failed");
+  if (at.staged) HIPCHK(hipMemcpyAsync(at.dev, at.user, at.bytes, hipMemcpyHostToDevice, b->stream));
+  P.mode = 0;
+  P.reg = regularization;
+  P.target = (const float*)at.dev;
+  P.qvel = (float*)aq.dev;
+  P.status = (int*)as.dev;
+  HIPCHK(dx_launch_dls((int)E, lds, b->stream, b->dm_dev, b->db, b->model->lds, P));
+  if (aq.staged) HIPCHK(hipMemcpyAsync(aq.user, aq.dev, aq.bytes, hipMemcpyDeviceToHost, b->stream));
+  if (as.staged) HIPCHK(hipMemcpyAsync(as.user, as.dev, as.bytes, hipMemcpyDeviceToHost, b->stream));
+  if (S) HIPCHK(hipStreamSynchronize(b->stream));
   return 0;
 }
 

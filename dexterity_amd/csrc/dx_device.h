@@ -853,6 +853,33 @@ __device__ __forceinline__ void mfma_chol_solve32(const float* A, int n, float d
   SYNC();
 }
 
+// Pre-pass of mfma_chol_solve32 for a caller that must know the matrix's numerical rank
+// (dx_dls.hip): runs the same factorisation on the padded tile C (the accumulator layout
+// above, as mfma_chol_solve32 loads it) and returns whether every pivot of the first n
+// columns -- the squared diagonal of the factor, before the 1e-30 clamp -- is above thr.
+// A NaN pivot counts as not above.  The result is wave-uniform (readlane values only).
+__device__ __forceinline__ bool mfma_chol_pivots32(dx_f16v C, int n, float thr) {
+  const int j = LANE & 31, hi = LANE >> 5;
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 32; k += 2) {
+    const int vk = 4 * (k >> 3) + (k & 3);
+    const bool up = (k & 7) >= 4;
+    const float rk = half_dup(C[vk], up), rk1 = half_dup(C[vk + 1], up);
+    const float p11 = rl(C[vk], k + (up ? 32 : 0));
+    const float i11 = __builtin_amdgcn_rsqf(fmaxf(p11, 1e-30f));
+    const float l21 = rl(C[vk + 1], k + (up ? 32 : 0)) * i11;
+    const float p22 = rl(C[vk + 1], k + 1 + (up ? 32 : 0)) - l21 * l21;
+    const float i22 = __builtin_amdgcn_rsqf(fmaxf(p22, 1e-30f));
+    ok = ok && (k >= n || p11 > thr) && (k + 1 >= n || p22 > thr);
+    const float lk = rk * i11;
+    const float lk1 = (rk1 - lk * l21) * i22;
+    const float p = j > k + 1 ? (hi ? lk1 : lk) : 0.f;
+    C = __builtin_amdgcn_mfma_f32_32x32x2f32(-p, p, C, 0, 0, 0);
+  }
+  return ok;
+}
+
 // Cholesky solve for 32 < n <= 64 on the matrix cores (two-hand scenes, nv 54).  The
 // padded 64 x 64 matrix is three 32 x 32 accumulator tiles: C11 (rows/cols 0-31),
 // C12 (rows 0-31, cols 32-63, i.e. the transpose of the lower off-diagonal block)

@@ -15,7 +15,7 @@
 // (mfma_chol_solve32), then qdot = J^T y.  That is dls.py's (J^T J + reg I) qdot =
 // J^T twist by the push-through identity (J^T J + reg I)^-1 J^T = J^T (J J^T +
 // reg I)^-1: a 15 x 15 system instead of nv x nv, with the same solution.
-#include "dx_device.h"
+#include "dx_jac.h"
 
 // IK block in LDS (words), appended after the model's own layout at P.blk.
 struct IkLds {
@@ -36,50 +36,15 @@ __host__ __device__ inline IkLds ik_lds(int blk, int nv) {
 }
 int dx_ik_lds_words(const DevModel& d, int) { return ik_lds(0, d.nv).total; }
 
-// lane t < 3 * nsite: coordinate t % 3 of site t / 3 at the current kinematics
-// (site_xpos, as geometry.PoseStamped(frame=site).get_world_pose reads it)
+// the fingertip sites as points (dx_jac.h): site_xpos, as
+// geometry.PoseStamped(frame=site).get_world_pose reads it, and mj_jacSite rows
 template <class Ctx>
 __device__ __forceinline__ void sites_to_lds(const Ctx& c, const IkDev& P, float* pt) {
-  const DevModel& m = c.mdl();
-  if (LANE < 3 * P.nsite) {
-    const int s = LANE / 3, e = LANE - 3 * s;
-    const int sid = P.sites[s];
-    const int b = m.site_bodyid[sid];
-    const float* xp = c.f(c.L.xpos) + 3 * b;
-    const float* xm = c.f(c.L.xmat) + 9 * b;
-    const DXG float* sp = m.site_pos + 3 * sid;
-    pt[LANE] = xp[e] + xm[3 * e] * sp[0] + xm[3 * e + 1] * sp[1] + xm[3 * e + 2] * sp[2];
-  }
-  SYNC();
+  points_to_lds(c, SitePoints{c.mdl(), P.sites}, P.nsite, pt);
 }
-
-// mj_jacSite rows [3 * nsite][nv]: translational (rot = false) or rotational.  Column
-// d of a site on body b is non-zero when dof d is on b's path to the root; then
-// jacp = cdof_lin + cdof_ang x (site - subtree_com[root]), jacr = cdof_ang.
 template <class Ctx>
 __device__ __forceinline__ void site_jacobian(const Ctx& c, const IkDev& P, const float* pt, float* J, bool rot) {
-  const DevModel& m = c.mdl();
-  const int nv = c.nv, n = 3 * P.nsite * nv;
-  const float* cdof = c.f(c.L.cdof);
-  const float* rcom = c.f(c.L.rcom);
-  for (int k = LANE; k < n; k += DX_WAVE) {
-    const int r = k / nv, d = k - r * nv, s = r / 3, e = r - 3 * s;
-    const int b = m.site_bodyid[P.sites[s]];
-    float v = 0.f;
-    if ((m.body_chain[b] >> d) & 1ull) {
-      const float* cd = cdof + 6 * d;
-      if (rot) {
-        v = cd[e];
-      } else {
-        const float* rc = rcom + 3 * m.body_rootidx[b];
-        const float o0 = pt[3 * s] - rc[0], o1 = pt[3 * s + 1] - rc[1], o2 = pt[3 * s + 2] - rc[2];
-        const float cr = e == 0 ? cd[1] * o2 - cd[2] * o1 : e == 1 ? cd[2] * o0 - cd[0] * o2 : cd[0] * o1 - cd[1] * o0;
-        v = cd[3 + e] + cr;
-      }
-    }
-    J[k] = v;
-  }
-  SYNC();
+  point_jacobian(c, SitePoints{c.mdl(), P.sites}, P.nsite, pt, J, rot);
 }
 
 // mj_integratePos(qpos, qdot, h) followed by mj_normalizeQuat, then the clip of the

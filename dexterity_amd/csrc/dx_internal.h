@@ -479,5 +479,25 @@ hipError_t dx_launch_ik(int nwave, size_t lds, hipStream_t stream, const DevMode
 hipError_t dx_launch_ik_select(int nenv, hipStream_t stream, const DevModel& m, const IkDev& P, float* qpos_out,
                                int* success, float* err_out, int* attempt_out, int* steps_out);
 
+// dx_dls.hip: object Jacobians and the damped-least-squares Cartesian-to-joint velocity
+// mapper (host side).  The controlled objects arrive resolved to points: a body and an
+// offset in its frame (a site's site_pos, a geom's geom_pos, zero for a body).
+#define DX_DLS_MAXPT 10      // 3 * npoint <= 32 rows of one 32 x 32 accumulator tile
+struct DlsDev {
+  int mode;                  // 0: joint velocities; 1: Jacobians
+  int npoint;
+  int blk;                   // LDS word offset of the mapper's block (after the model's layout)
+  float reg;                 // regularization weight (lambda >= 0)
+  int body[DX_DLS_MAXPT];
+  float off[3 * DX_DLS_MAXPT];
+  const float* target;       // mode 0: [nenv][npoint][3]
+  float* qvel;               // mode 0: [nenv][nv]
+  int* status;               // mode 0: [nenv] (may be null)
+  float *jacp, *jacr;        // mode 1: [nenv][npoint][3][nv] (either may be null)
+};
+int dx_dls_lds_words(const DevModel& d);
+hipError_t dx_launch_dls(int nenv, size_t lds, hipStream_t stream, const DevModel* mdev, const DevBatch& B,
+                         const Lds& L, const DlsDev& P);
+
 // dx_observe.hip: the optional hand observables' gather, queued behind the step's launches
 hipError_t dx_launch_hand_obs(hipStream_t stream, const HandObs& H);

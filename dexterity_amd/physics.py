@@ -136,6 +136,22 @@ class BatchedPhysics:
                                            None if jr is None else jr.ctypes.data))
         return jp, jr
 
+    def jac_object(self, types, ids, rotational: bool = True):
+        """mj_jacBody / mj_jacGeom / mj_jacSite for every env at its current qpos
+        (utils/mujoco_utils.py:38-73, compute_object_6d_jacobian, for the object types of
+        controllers/mapper.py:60-64): types are `_lib.OBJ_BODY` / `OBJ_GEOM` / `OBJ_SITE`
+        per object; (jacp, jacr) of shape [B, nobj, 3, nv]."""
+        t = np.ascontiguousarray(types, dtype=np.int32).reshape(-1)
+        i = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        if len(t) != len(i):
+            raise ValueError("one object type per object id")
+        shape = (self.nenv, len(i), 3, self.model.nv)
+        jp = np.empty(shape, np.float32)
+        jr = np.empty(shape, np.float32) if rotational else None
+        _lib.check(_lib.load().dx_jac_object(self.ptr, t.ctypes.data, i.ctypes.data, len(i), jp.ctypes.data,
+                                             None if jr is None else jr.ctypes.data))
+        return jp, jr
+
     def enable_sensors(self, enable: bool = True) -> None:
         """Joint torque sensors (DX_SENSOR_TORQUE) computed by every step / forward."""
         _lib.check(_lib.load().dx_sensor_enable(self.ptr, int(enable)))

@@ -454,6 +454,43 @@ int dx_ik_solve(dx_batch* b, const dx_ik_options* opt, const int32_t* sites, int
                 const int32_t* joints, int32_t njoint, const float* targets, float* qpos_out,
                 int32_t* success, float* linear_err, int32_t* attempt, int32_t* steps);
 
+/* Cartesian-to-joint velocity mapping ------------------------------------- */
+/* The controlled objects of dx_jac_object / dx_dls_map: bodies, geoms and sites
+ * (controllers/mapper.py:57-81), each a (type, id) pair.  A body is controlled at its
+ * frame origin xpos (mj_jacBody), a geom at geom_xpos (mj_jacGeom), a site at site_xpos
+ * (mj_jacSite).  3 * nobj <= 32 and nv <= 64, else DX_ELIMIT; an unknown type, an id out
+ * of range or nobj < 1 is DX_EINVAL.  Every argument error returns before any launch.
+ *
+ * Host or device arguments: the work is enqueued on the batch's stream.  Each data array
+ * (jacp, jacr, target_vel, qvel_out, status) that is device memory is read or written in
+ * place by the kernel; one that is host memory is staged through device scratch.  A call
+ * whose data arrays are all device memory returns without synchronising (dx_sync, or any
+ * later call on the batch, orders after it); a call with a host array synchronises the
+ * stream before it returns.  (dx_jac_site and dx_ik_solve stage every array and always
+ * synchronise.)  types / ids are always host memory and are consumed before the return. */
+enum dx_obj_type { DX_OBJ_BODY = 1, DX_OBJ_GEOM = 5, DX_OBJ_SITE = 6 };   /* MuJoCo's mjtObj values */
+/* compute_object_6d_jacobian (utils/mujoco_utils.py:38-73) for bodies, geoms and sites of
+ * every env at its current qpos (kinematics + com positions are recomputed first; the
+ * batch's state is not modified): jacp / jacr [nenv][nobj][3][nv] f32, host or device
+ * memory, either may be null.  For sites the values equal dx_jac_site's bit for bit. */
+int dx_jac_object(dx_batch* b, const int32_t* types, const int32_t* ids, int32_t nobj,
+                  float* jacp, float* jacr);
+/* DampedLeastSquaresMapper.compute_joint_velocities (controllers/dls/dls.py:43-77) for
+ * every env at its current qpos: with J [3 * nobj][nv] the stacked translational Jacobians
+ * (the rotational halves are dropped, dls.py:62) and V = target_vel,
+ *   qvel_out = J^T (J J^T + regularization I)^-1 V,
+ * the solution of dls.py:69-74's (J^T J + regularization I) qdot = J^T V; with
+ * regularization = 0 (dls.py:75-77, np.linalg.lstsq) the minimum-norm solution for a J of
+ * full row rank.  A dof no object depends on gets exactly 0.
+ * Rank guard (a deviation from lstsq, which would return a least-squares solution): when a
+ * Cholesky pivot of J J^T + regularization I is <= eps_fp32 * max(3 * nobj, nv) * its
+ * largest diagonal entry, the env's status is 1 and its qvel_out row is all zeros.
+ * target_vel [nenv][nobj][3], qvel_out [nenv][nv], status [nenv] int32 (0 ok, 1
+ * rank-deficient; may be null); host or device memory.  A negative or non-finite
+ * regularization is DX_EINVAL.  The batch's state is not modified. */
+int dx_dls_map(dx_batch* b, const int32_t* types, const int32_t* ids, int32_t nobj,
+               float regularization, const float* target_vel, float* qvel_out, int32_t* status);
+
 /* Timing ---------------------------------------------------------------- */
 /* When enabled, HIP events bracket the step-kernel launches on the batch stream -- every
  * launch (enable = 1) or every enable-th one (enable > 1: the events' own packets cost
