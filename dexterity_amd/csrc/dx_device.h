@@ -11,26 +11,41 @@
 // The lane id is laundered through an empty volatile asm at every use: the compiler
 // can then neither hoist lane-dependent address arithmetic out of the substep loop
 // nor keep it alive across the stages (it did, and spilled those values to scratch).
-__device__ __forceinline__ int lane_id() {
+// The laundering also hides the lane id's range, so a guard that a constant n and the
+// lane's half decide stays a compare and an exec-mask block of its own, and a
+// `for (i = LANE; i < n; i += DX_WAVE)` over a constant n <= DX_WAVE stays a loop.
+// lane_id_t<true> states the range again (no instruction).
+template <bool RANGED>
+__device__ __forceinline__ int lane_id_t() {
   int l = (int)threadIdx.x;
   asm volatile("" : "+v"(l));
+  if (RANGED) __builtin_assume((unsigned)l < (unsigned)DX_WAVE);
   return l;
 }
-#define LANE (lane_id())
-// The laundering also hides the lane id's range, so a guard that a constant n and the
-// lane's half decide stays a compare and an exec-mask block of its own.  lane_ranged()
-// states the range again (no instruction); lane_clamped(n) is the lane's index into n
-// entries for a load that every lane issues and selects after (n == 0 reads entry 0).
-// Not the default LANE: with the range known a `for (i = LANE; i < n; i += DX_WAVE)` over
-// a constant n becomes straight-line code, and the compiler then contracts other
-// multiply-add pairs around it -- the specialized kernels' results change in the last bit
-// ("lane guards").
-__device__ __forceinline__ int lane_ranged() {
-  const int l = lane_id();
-  __builtin_assume((unsigned)l < (unsigned)DX_WAVE);
-  return l;
-}
-__device__ __forceinline__ int lane_clamped(int n) { return min(lane_id(), max(n - 1, 0)); }
+// LANE states the range in the stage groups that DX_LANE_RANGE_MASK names, one bit per
+// group; the sources set DX_LANE_GROUP where a group begins.  Only dx_step.hip defines a
+// mask: with the range known the blocks that merge let -ffp-contract=fast pair other
+// multiplies and adds, the step kernel's results are pinned bit for bit by goldens
+// (tests/test_gpu_guard_golden.py, test_gpu_lane_golden.py), and a group is ranged only
+// once tools/fp_census.py shows no fusion moved against the parent (DESIGN section 8,
+// "lane range").  The kinematic-query, DLS, sensor and observation units have no such
+// golden and keep the unranged id.
+#define DX_LG_TREE 0        // context, kinematics, com, tendons, CRB, velocity stage
+#define DX_LG_COLLISION 1   // broadphase, narrowphase
+#define DX_LG_CONSTRAINT 2  // make_constraint
+#define DX_LG_SOLVER 3      // Cholesky solvers, Newton / CG / PGS and their glue
+#define DX_LG_EULER 4       // forward, euler, observe
+#define DX_LG_TASK 5        // task logic, draws, env begin / finish, the queue
+#ifndef DX_LANE_RANGE_MASK
+#define DX_LANE_RANGE_MASK 0
+#endif
+#define DX_LANE_GROUP DX_LG_TREE
+#define LANE (lane_id_t<(((DX_LANE_RANGE_MASK) >> (DX_LANE_GROUP)) & 1) != 0>())
+// lane_ranged() states the range in every unit (the MFMA Cholesky sweeps, shared with
+// the query kernels); lane_clamped(n) is the lane's index into n entries for a load that
+// every lane issues and selects after (n == 0 reads entry 0).
+__device__ __forceinline__ int lane_ranged() { return lane_id_t<true>(); }
+__device__ __forceinline__ int lane_clamped(int n) { return min(lane_id_t<false>(), max(n - 1, 0)); }
 // A workgroup is exactly one wavefront, and a wavefront's LDS instructions execute
 // in issue order, so cross-lane LDS hand-offs need only a compiler-level barrier
 // (no s_barrier, and no s_waitcnt on outstanding global stores).
@@ -715,6 +730,8 @@ __device__ __forceinline__ void crb_mass(const Ctx& c) {
   SYNC();
 }
 
+#undef DX_LANE_GROUP
+#define DX_LANE_GROUP DX_LG_SOLVER
 // In-place dense Cholesky (lower, row-major) of the n x n matrix A, one wave.
 // Column k: lanes scale the sub-diagonal of column k, then update the trailing
 // lower triangle; entry t of a w x w trailing triangle maps to (ii, jj) through

@@ -17,10 +17,18 @@
 // The restated MuJoCo semantics, and where the reference configures each stage,
 // are listed in oracle/dx_oracle.c (the fp64 CPU oracle these kernels are
 // parity-tested against) and DESIGN.md §3.
+// The stage groups whose LANE states its range (dx_device.h DX_LG_*): every group but
+// make_constraint (bit 2), whose multiplies and adds pair differently once its lane loops
+// are straight-line code (tools/fp_census.py: row_params / impedance).
+#ifndef DX_LANE_RANGE_MASK
+#define DX_LANE_RANGE_MASK 0x3b
+#endif
 #include "dx_device.h"
 #include "dx_task.h"
 #include <utility>
 
+#undef DX_LANE_GROUP
+#define DX_LANE_GROUP DX_LG_COLLISION
 // 16-byte write-through (sc1) store into a per-env block whose base is wave-uniform:
 // the substep queue hands these bytes to the env's next task without a release fence
 // (MI355X guide, Guideline 16 R1: sc1 payload, vmcnt(0), flag; the consumer acquires).
@@ -1419,6 +1427,8 @@ __device__ __forceinline__ void collision(const Ctx& c, int watch_only, int wg, 
   stage_mark(c, ST_NARROW);
 }
 
+#undef DX_LANE_GROUP
+#define DX_LANE_GROUP DX_LG_CONSTRAINT
 // ------------------------------------------------------------------------ //
 // constraints
 // ------------------------------------------------------------------------ //
@@ -1757,6 +1767,8 @@ __device__ __forceinline__ void make_constraint(const Ctx& c) {
   SYNC();
 }
 
+#undef DX_LANE_GROUP
+#define DX_LANE_GROUP DX_LG_TREE
 // ------------------------------------------------------------------------ //
 // velocity stage: comVel, RNE (+ applied wrench), passive, actuation
 // ------------------------------------------------------------------------ //
@@ -1908,6 +1920,8 @@ __device__ __forceinline__ void velocity_stage(const Ctx& c, const float* xfrc) 
   SYNC();
 }
 
+#undef DX_LANE_GROUP
+#define DX_LANE_GROUP DX_LG_SOLVER
 // ------------------------------------------------------------------------ //
 // Newton solver
 // ------------------------------------------------------------------------ //
@@ -2874,7 +2888,7 @@ __device__ __forceinline__ void solve_cg(const Ctx& c, float scale, float tol) {
     float gn = 0;
     for (int i = LANE; i < nv; i += DX_WAVE) {
       grad[i] = Ma[i] - qs[i] - grad[i];
-      gn += grad[i] * grad[i];
+      gn = fmaf(grad[i], grad[i], gn);  // (pinned: one trip over a constant nv would leave a bare multiply)
     }
     gn = sqrtf(wave_sum(gn)) * scale;
     SYNC();
@@ -3495,7 +3509,7 @@ __device__ __forceinline__ void solve(const Ctx& c) {
     float gn = 0;
     for (int i = LANE; i < nv; i += DX_WAVE) {
       grad[i] = Ma[i] - qs[i] - grad[i];
-      gn += grad[i] * grad[i];
+      gn = fmaf(grad[i], grad[i], gn);  // (pinned: one trip over a constant nv would leave a bare multiply)
     }
     gn = sqrtf(wave_sum(gn)) * scale;
     stage_mark(c, ST_NEWTON_GRAD);
@@ -3561,6 +3575,8 @@ __device__ __forceinline__ void solve(const Ctx& c) {
 // forward + Euler
 // ------------------------------------------------------------------------ //
 
+#undef DX_LANE_GROUP
+#define DX_LANE_GROUP DX_LG_EULER
 template <class Ctx>
 __device__ __forceinline__ void forward(const Ctx& c, const float* xfrc) {
   const DevModel& m = c.mdl();
@@ -3717,6 +3733,8 @@ __device__ __forceinline__ void observe(const Ctx& c, const DevBatch& B, int env
   }
 }
 
+#undef DX_LANE_GROUP
+#define DX_LANE_GROUP DX_LG_TASK
 // ------------------------------------------------------------------------ //
 // reach: fingertip goals and collision-free joint angles (mode 2 pass)
 // ------------------------------------------------------------------------ //
