@@ -3133,17 +3133,19 @@ __device__ __forceinline__ void solve_pgs_ar(const Ctx& c, float scale, float to
     idg[B] = 1.0f / dg;
     static_for([&](auto K) { A[B][K.value] *= idg[B]; }, rows);
   }, blocks);
+  // w (lane d: w[d]) from every row's current force; wt, the tail rows' part, starts
+  // from their forces on entry (a kept warm start's are nonzero) and is kept current by
+  // their updates
+  float wt = 0.f, wl = 0.f;
   float ardt = 1.f;  // lane t: AR of tail row NB x 64 + t on the diagonal
   for (int t = 0; t < ntail; t++) {
     const int r = NB * DX_PGS_AR + t;
     const float p = pgs_p_lane(c, r, G);
     const float s = wave_sum(p * p) + 1.0f / D[r];
     ardt = LANE == t ? s : ardt;
+    wt = fmaf(f[r], p, wt);
   }
   stage_mark(c, ST_NEWTON_HESS);
-  // w (lane d: w[d]) from every row's current force; wt, the tail rows' part, is kept
-  // current by their updates
-  float wt = 0.f, wl = 0.f;
   auto wsum = [&]() {
     float t[32];
 #pragma unroll

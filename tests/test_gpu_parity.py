@@ -1464,29 +1464,46 @@ def test_pgs_solver_parity(gpu, oracle_mod, reorient_setup):
         phys.close()
 
 
-def test_pgs_tail_rows_parity(gpu, oracle_mod):
-    """PGS past 128 constraint rows: the AR path's tail rows (dx_step.hip solve_pgs, rows
-    128+ one at a time on qacc after the two register blocks).  The reorient envs of the
-    bench's state mix with 27 or more contacts (24 friction-loss rows + 4 pyramid edges per
-    contact: more than 128 rows, the envs that set the PGS launch) take one forward pass
-    with <option solver="PGS">: run to convergence, kernel vs the oracle's PGS
-    within PGS_CONV_MAX (test_pgs_solver_parity); at MuJoCo's defaults (100 sweeps, not
-    converged on these states), kernel vs oracle within PGS_TAIL_MAX.  Both on the GPU's
-    own contact list (dxo_set_contacts)."""
+def test_pgs_tail_rows_parity(gpu, oracle_mod, monkeypatch):
+    """PGS past its register blocks: the AR path's tail rows (dx_step.hip solve_pgs_ar, rows
+    NB*64.. one at a time in whitened force space after the NB register blocks).  The tail
+    starts at row 128 in the generic kernel and the mid tier (NB 2) and at row 192 in the
+    reorient PGS specialisation and the overflow tier (NB 3).  The specialisation's pool
+    holds 32 contacts (24 friction-loss rows + limits + 4 pyramid edges per contact: 160
+    rows at the most), so at default settings it never has a tail; a non-default
+    `iterations` or DX_GENERIC_KERNEL=1 selects the generic kernel, which has one from 27
+    contacts on.  The reorient envs of the bench's state mix with 27 or more contacts take
+    one forward pass with <option solver="PGS">:
+      * run to convergence (the generic kernel), kernel vs the oracle's PGS within
+        PGS_CONV_MAX (test_pgs_solver_parity);
+      * at MuJoCo's defaults (100 sweeps, not converged on these states), kernel vs oracle
+        within PGS_TAIL_MAX -- the specialisation, and the generic kernel on the states
+        with 32 or fewer contacts and more than 128 rows (a tail, at least two states);
+      * on those states, the generic kernel at defaults from a warm start that is kept by
+        construction (tests/pgs_cases.py: w* + eps (qacc_smooth - w*), eps 0 and 1e-3, w*
+        the Newton optimum), so that tail rows start from nonzero forces, within
+        PGS_TAIL_MAX: the hand scene's mixed friction-loss, limit and contact rows.
+    All on the GPU's own contact list (dxo_set_contacts)."""
     from dexterity_amd import manipulation
+    from tests import pgs_cases as pc
 
+    monkeypatch.delenv("DX_GENERIC_KERNEL", raising=False)
     n = 4096
     env = manipulation.load("reorient", "state_dense", seed=1, num_envs=n)
     env.reset()
-    states = []
+    states, small = [], 0
     for step in range(80):
         env.step_random(step)
         ph = env.physics
-        sel = np.nonzero(ph.get(_lib.NCON)[:, 0] >= 27)[0][:3]
+        nc = ph.get(_lib.NCON)[:, 0]
+        # (27..31 contacts: a tail in the generic kernel, within the step kernel's pool)
+        sel = list(np.nonzero(nc >= 27)[0][:3]) if len(states) < 6 else []
+        sel += [e for e in np.nonzero((nc >= 27) & (nc <= 31))[0][:3] if e not in sel and small < 3]
         if len(sel):
             q, v, w, u = ph.qpos, ph.qvel, ph.get(_lib.QACC_WARMSTART), ph.get(_lib.CTRL)
             states += [tuple(np.asarray(x[e], dtype=np.float64) for x in (q, v, w, u)) for e in sel]
-        if len(states) >= 6:
+            small += sum(27 <= nc[e] <= 31 for e in sel)
+        if len(states) >= 6 and small >= 3:
             break
     xfrc = env.task.gravity_compensation
     cm = env.task.compiled
@@ -1497,12 +1514,18 @@ def test_pgs_tail_rows_parity(gpu, oracle_mod):
     assert sum(k > 128 for k in nefc) >= 2, nefc
     # on the GPU's own contact list (dxo_set_contacts): the deep contacts of these grasps
     # move under fp32 MPR (the full-batch test's "geometry" states); the solver is the test
-    def run(model_cm):
-        phys = _load_states(gpu, gpu.Model(model_cm), xfrc, states)
+    counts = []
+
+    def run(model_cm, sts=None):
+        phys = _load_states(gpu, gpu.Model(model_cm), xfrc, states if sts is None else sts)
         phys.debug(True)
+        phys.health_clear()
         phys.forward()
         phys.sync()
         con, qacc = phys.debug_get("contact"), phys.qacc
+        counts[:] = [phys.get(_lib.NCON)[:, 0], phys.debug_get("efc_count")[:, 0], phys.get(_lib.NITER)[:, 0]]
+        h = phys.health()
+        assert h["contact_overflow"] == 0 and h["row_overflow"] == 0 and h["diverged"] == 0, h
         phys.close()
         return con, qacc
 
@@ -1529,6 +1552,43 @@ def test_pgs_tail_rows_parity(gpu, oracle_mod):
     # oracle's own PGS stays as far from it -- so Newton is reported, not asserted)
     assert e_pg[ok].max() <= PGS_CONV_MAX
     assert ea[ok].max() <= PGS_TAIL_MAX
+    # the generic kernel (NB 2) at defaults: the states whose rows reach its tail
+    monkeypatch.setenv("DX_GENERIC_KERNEL", "1")
+    con, qacc = run(pgd)
+    ncon_g, nefc_g = counts[0].copy(), counts[1].copy()
+    tail = np.nonzero((ncon_g <= 32) & (nefc_g > 128))[0]
+    print(f"generic kernel: ncon {ncon_g.tolist()} nefc {nefc_g.tolist()}, tail states {tail.tolist()}")
+    assert len(tail) >= 2, (ncon_g, nefc_g)
+    eg = np.array([err(om_d, con, qacc, e, states[e]) for e in tail])
+    print(f"PGS tail, defaults, generic kernel: |qacc| err / scale {np.round(eg, 7).tolist()}")
+    assert eg.max() <= PGS_TAIL_MAX
+    # ... and from a warm start that is kept: tail rows that start from nonzero forces
+    x32 = np.asarray(xfrc, dtype=np.float32).astype(np.float64)
+    for eps in (0.0, 1e-3):
+        sts, ref = [], []
+        for e in tail:
+            q, v, _, u = states[e]
+            gc = con[e, : ncon_g[e]].astype(np.float64)
+            dn = pc.oracle_at(oracle_mod, om, q, v, warm=states[e][2], contacts=gc, ctrl=u, xfrc=x32)
+            warm = pc.f32(pc.warm_start(dn.qacc, dn.qacc_smooth, eps))
+            d = pc.oracle_at(oracle_mod, om_d, q, v, warm=warm, contacts=gc, ctrl=u, xfrc=x32)
+            p = pc.Problem(d, pgd)
+            f0 = p.warm_forces(warm)
+            sts.append((q, v, warm, u))
+            ref.append((d.qacc.copy(), max(1.0, np.abs(d.qacc_smooth).max()), d.nefc, d.niter, p.dual_cost(f0),
+                        np.count_nonzero(f0[128:])))
+        con_w, qacc_w = run(pgd, sts)
+        ew = []
+        for k, e in enumerate(tail):
+            np.testing.assert_array_equal(con_w[k], con[e])
+            assert counts[1][k] == ref[k][2] == nefc_g[e]
+            ew.append(np.abs(qacc_w[k] - ref[k][0]).max() / ref[k][1])
+            print(f"PGS tail, kept warm start, eps {eps:g}, state {e}: nefc {ref[k][2]}, {ref[k][5]} of {ref[k][2] - 128} tail "
+                  f"rows start nonzero, dual cost {ref[k][4]:.3g}, sweeps {counts[2][k]} (oracle {ref[k][3]}), "
+                  f"|qacc| err / scale {ew[-1]:.2e}")
+        for k in range(len(tail)):
+            assert ref[k][4] < 0 and ref[k][5] > 0, (eps, ref[k][2:])
+        assert max(ew) <= PGS_TAIL_MAX, (eps, ew)
 
 
 # PGS bounds.  Measured (r4) over the 12 states: converged (3000 sweeps, 1e-13) qacc
@@ -1539,7 +1599,9 @@ PGS_CONV_MAX = 5e-4
 PGS_QACC_MED, PGS_QACC_MAX = 2e-4, 1e-3
 PGS_QPOS_MAX, PGS_QVEL_MAX = 1e-6, 1e-5
 # tail states (r5, 7 states, nefc 128-144, on the GPU's contacts): converged max 2.4e-5,
-# defaults max 2.9e-5 of the scale
+# defaults max 2.9e-5 of the scale; generic kernel at defaults (6 states with a tail) max
+# 4.3e-5, from a kept warm start (eps 0 / 1e-3) max 4.5e-5 / 8.6e-6; the synthetic
+# dispatch cases (test_gpu_pgs_dispatch.py) max 5.0e-6
 PGS_TAIL_MAX = 1e-4
 
 
