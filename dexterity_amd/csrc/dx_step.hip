@@ -1985,15 +1985,20 @@ __device__ __forceinline__ void mrow_load(const float* M, int n, float (&mr)[30]
     mr[k] = LANE < n && k < n ? t : 0.f;
   }
 }
-__device__ __forceinline__ void mat_vec_rows(const float (&mr)[30], const float* x, float* y, int n) {
-  const float xi = x[min(LANE, n - 1)];
+// (mr v) of this lane's row, v held one element per lane: even and odd columns in two
+// accumulators, summed at the end
+__device__ __forceinline__ float mrow_dot(const float (&mr)[30], float v) {
   float s0 = 0.f, s1 = 0.f;
 #pragma unroll
   for (int k = 0; k < 30; k += 2) {
-    s0 = fmaf(mr[k], rl(xi, k), s0);
-    s1 = fmaf(mr[k + 1], rl(xi, k + 1), s1);
+    s0 = fmaf(mr[k], rl(v, k), s0);
+    s1 = fmaf(mr[k + 1], rl(v, k + 1), s1);
   }
-  if (LANE < n) y[LANE] = s0 + s1;
+  return s0 + s1;
+}
+__device__ __forceinline__ void mat_vec_rows(const float (&mr)[30], const float* x, float* y, int n) {
+  const float s = mrow_dot(mr, x[min(LANE, n - 1)]);
+  if (LANE < n) y[LANE] = s;
 }
 __device__ float dx_mrow_none[30];  // (the reference line_search / eval_cost take when MREG is off)
 
@@ -2053,47 +2058,39 @@ __device__ __forceinline__ void jac_rows(const Ctx& c, const float* x, float* ou
   SYNC();
 }
 
+// What row_force / row_cost take of row r: its type and D, and the friction-loss rows'
+// (rows [0, nfric)) floss and R floss, 0 on every other row
+struct RowP { int type; float D, fl, Rf; };
+template <class Ctx>
+__device__ __forceinline__ RowP row_params_at(const Ctx& c, int r) {
+  const bool fr = r < c.nfric;
+  return {((const int*)c.f(c.L.efc_meta))[r] & 15, c.f(c.L.efc_D)[r], fr ? c.f(c.L.efc_fl)[r] : 0.f,
+          fr ? c.f(c.L.efc_Rf)[r] : 0.f};
+}
+
 // sum of the constraint rows' costs at residuals jr (+ g0, the Gauss term)
 template <class Ctx>
 __device__ __forceinline__ float rows_cost(const Ctx& c, const float* jr, float g0) {
-  const DevModel& m = c.mdl();
-  int nefc = c.I[I_NEFC];
-  const int* meta = (const int*)c.f(c.L.efc_meta);
-  const float* D = c.f(c.L.efc_D);
-  const float* fl = c.f(c.L.efc_fl);
-  const float* Rf = c.f(c.L.efc_Rf);
+  const int nefc = c.I[I_NEFC];
   float g = g0;
   for (int r = LANE; r < nefc; r += DX_WAVE) {
     float f, hw;
-    bool fr = r < c.nfric;
-    g += row_cost(meta[r] & 15, D[r], fr ? fl[r] : 0.f, fr ? Rf[r] : 0.f, jr[r], f, hw);
+    const RowP p = row_params_at(c, r);
+    g += row_cost(p.type, p.D, p.fl, p.Rf, jr[r], f, hw);
   }
-  (void)m;
   return wave_sum(g);
 }
 
 // cost at the current jar (efc_jar) + gauss; fills nothing else.  Returns total.
 template <class Ctx>
 __device__ __forceinline__ float total_cost(const Ctx& c, const float* qacc, const float* Ma, float* gauss = nullptr) {
-  const DevModel& m = c.mdl();
   int nv = c.nv;
   const float* qs = c.f(c.L.qfrc_smooth);
   const float* a0 = c.f(c.L.qacc_smooth);
   float g = 0;
   for (int i = LANE; i < nv; i += DX_WAVE) g += 0.5f * (qacc[i] - a0[i]) * (Ma[i] - qs[i]);
   if (gauss) *gauss = wave_sum(g);
-  int nefc = c.I[I_NEFC];
-  const int* meta = (const int*)c.f(c.L.efc_meta);
-  const float* D = c.f(c.L.efc_D);
-  const float* fl = c.f(c.L.efc_fl);
-  const float* Rf = c.f(c.L.efc_Rf);
-  const float* jar = c.f(c.L.efc_jar);
-  for (int r = LANE; r < nefc; r += DX_WAVE) {
-    float f, hw;
-    bool fr = r < c.nfric;
-    g += row_cost(meta[r] & 15, D[r], fr ? fl[r] : 0.f, fr ? Rf[r] : 0.f, jar[r], f, hw);
-  }
-  return wave_sum(g);
+  return rows_cost(c, c.f(c.L.efc_jar), g);
 }
 
 // jar = J qacc - aref, Ma = M qacc; returns cost
@@ -2453,7 +2450,7 @@ __device__ __forceinline__ int row_zone(int type, float Rf, float jar) {
 // solver needs no separate cost pass.
 // HAVE_MDIR: the caller already holds M dir in v4 (CG's recurrence), no product here.
 // MREG: M's rows in registers (mrow_load), the product without LDS.
-template <bool NEWTON = false, bool HAVE_MDIR = false, bool MREG = false, bool HAVE_JV = false, class Ctx>
+template <bool NEWTON = false, bool HAVE_MDIR = false, bool MREG = false, class Ctx>
 __device__ __forceinline__ float line_search(const Ctx& c, const float* qacc, const float* Ma, const float* dir, int* changed,
                                              float* slope0 = nullptr, const float* grad = nullptr,
                                              float gauss = 0.f, float* cost_new = nullptr, float* gauss_new = nullptr,
@@ -2467,10 +2464,8 @@ __device__ __forceinline__ float line_search(const Ctx& c, const float* qacc, co
     stage_mark(c, ST_MATVEC);
   }
   float* jv = c.f(c.L.efc_jv);
-  if (!HAVE_JV) {  // (HAVE_JV: the caller has J dir in efc_jv)
-    jac_vec(c, dir, jv);  // includes SYNC
-    stage_mark(c, ST_JACVEC);
-  }
+  jac_vec(c, dir, jv);  // includes SYNC
+  stage_mark(c, ST_JACVEC);
   const float* qs = c.f(c.L.qfrc_smooth);
   float qa = 0, qb = 0, qg = 0;
   for (int i = LANE; i < nv; i += DX_WAVE) {
@@ -2603,6 +2598,7 @@ __device__ __forceinline__ void solve_cg_reg(const Ctx& c, float scale, float to
   float D[2], fl[2], Rf[2], ja[2], jj[2];
 #pragma unroll
   for (int h = 0; h < 2; h++) {
+    // (a clamped row, masked after the load -- not row_params_at, whose guard is on the index)
     const int r = lane + DX_WAVE * h, rc = min(r, nefc - 1);
     const bool ok = r < nefc, fr = ok && r < c.nfric;
     ty[h] = ok ? (meta[rc] & 15) : DXR_CON;
@@ -2619,15 +2615,6 @@ __device__ __forceinline__ void solve_cg_reg(const Ctx& c, float scale, float to
         for (int d = 0; d < 30; d++) Jd[h][d] = d == e ? Jd[h][d] + v : Jd[h][d];
       });
   }
-  auto rows_of = [&](const float (&mr)[30], float v) {  // (mr v) of this lane's row
-    float y0 = 0.f, y1 = 0.f;
-#pragma unroll
-    for (int e = 0; e < 30; e += 2) {
-      y0 = fmaf(mr[e], rl(v, e), y0);
-      y1 = fmaf(mr[e + 1], rl(v, e + 1), y1);
-    }
-    return y0 + y1;
-  };
   auto jt_force = [&]() {  // (J'f)_d of the rows' forces at the residuals ja
     float t[32];
 #pragma unroll
@@ -2663,7 +2650,7 @@ __device__ __forceinline__ void solve_cg_reg(const Ctx& c, float scale, float to
     }
   };
   float grad = ma - q0 - jt_force();
-  float mg = rows_of(trow, grad);
+  float mg = mrow_dot(trow, grad);
   float dir = -mg, mdir = -grad;
   float gmg_old = wave_sum(grad * mg);
   int it = 0;
@@ -2709,7 +2696,7 @@ __device__ __forceinline__ void solve_cg_reg(const Ctx& c, float scale, float to
     const float impr = -0.5f * scale * alpha * g0;
     grad = ma - q0 - jt_force();
     const float gn = sqrtf(wave_sum(grad * grad)) * scale;
-    mg = rows_of(trow, grad);
+    mg = mrow_dot(trow, grad);
     stage_mark(c, ST_NEWTON_GRAD);
     if (impr < tol || gn < tol) {
       it++;
@@ -2725,8 +2712,8 @@ __device__ __forceinline__ void solve_cg_reg(const Ctx& c, float scale, float to
     // (the recurrences hold only as far as M M^-1 = I: M qacc and M dir exactly on a
     // restart and every 8 iterations, as solve_cg)
     if (restart || (it & 7) == 7) {
-      ma = rows_of(mrow, x);
-      mdir = rows_of(mrow, dir);
+      ma = mrow_dot(mrow, x);
+      mdir = mrow_dot(mrow, dir);
     }
   }
   if (dof) { qacc[lane] = x; Ma[lane] = ma; }
@@ -2776,74 +2763,10 @@ __device__ __forceinline__ void solve_cg(const Ctx& c, float scale, float tol) {
       chol_solve(M, nv, Mg, T);
     }
   };
-  // J's rows dense in registers (lane r: rows r and 64 + r, up to 128 rows, nv <= 30):
-  // J dir is then one FMA per dof with dir broadcast from LDS, and J'f a reduce-scatter of
-  // every lane's f_r J_r over the wave (wave_reduce_scatter32) -- no contact-frame passes,
-  // no LDS atomics.  (Other sizes keep jac_vec / jac_t_force.)
-  const int nefc = c.I[I_NEFC];
-  const bool jreg = DX_SWEEP && nv <= 30 && nefc <= 2 * DX_WAVE;
-  const int lane = LANE;
-  float Jd[2][30];
-#pragma unroll
-  for (int d = 0; d < 30; d++) Jd[0][d] = Jd[1][d] = 0.f;
-  if (jreg) {
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-      const int r = lane + DX_WAVE * h;
-      if (DX_WAVE * h < nefc)
-        pgs_row_nz(c, r < nefc ? r : -1, [&](int e, float v) {  // (v = 0 from lanes without a nonzero here)
-#pragma unroll
-          for (int d = 0; d < 30; d++) Jd[h][d] = d == e ? Jd[h][d] + v : Jd[h][d];
-        });
-    }
-  }
-  auto jdir = [&](const float* x, float* out) {  // out[r] = J_r x
-    float xs[30];
-#pragma unroll
-    for (int d = 0; d < 30; d++) xs[d] = x[min(d, nv - 1)];  // (uniform addresses: broadcast reads)
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-      if (DX_WAVE * h < nefc) {
-        float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-        for (int d = 0; d < 30; d += 2) {
-          s0 = fmaf(Jd[h][d], d < nv ? xs[d] : 0.f, s0);
-          s1 = fmaf(Jd[h][d + 1], d + 1 < nv ? xs[d + 1] : 0.f, s1);
-        }
-        const int r = lane + DX_WAVE * h;
-        if (r < nefc) out[r] = s0 + s1;
-      }
-    }
-    SYNC();
-  };
-  const int* meta = (const int*)c.f(c.L.efc_meta);
-  const float* Dp = c.f(c.L.efc_D);
-  const float* flp = c.f(c.L.efc_fl);
-  const float* Rfp = c.f(c.L.efc_Rf);
-  auto jtf = [&](float* out) {  // out = J'f, f the rows' forces at jar
-    float t[32];
-#pragma unroll
-    for (int d = 0; d < 32; d++) t[d] = 0.f;
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-      if (DX_WAVE * h < nefc) {
-        const int r = lane + DX_WAVE * h, rc = min(r, nefc - 1);
-        const bool fr = r < c.nfric;
-        float f, hw;
-        row_force(meta[rc] & 15, Dp[rc], fr ? flp[rc] : 0.f, fr ? Rfp[rc] : 0.f, jar[rc], f, hw);
-        f = r < nefc ? f : 0.f;
-#pragma unroll
-        for (int d = 0; d < 30; d++) t[d] = fmaf(f, Jd[h][d], t[d]);
-      }
-    }
-    const float w = wave_reduce_scatter32(t);  // component LANE >> 1
-    const float wd = __int_as_float(__builtin_amdgcn_ds_bpermute(8 * (lane & 31), __float_as_int(w)));
-    if (lane < nv) out[lane] = wd;
-    SYNC();
-  };
+  // (J x and J'f go through jac_vec / jac_t_force: the sizes whose J fits in registers
+  // run solve_cg_reg instead, see solve)
   int it = 0;
-  if (jreg) jtf(grad);
-  else jac_t_force(c, grad);  // grad <- J^T f
+  jac_t_force(c, grad);  // grad <- J^T f
   for (int i = LANE; i < nv; i += DX_WAVE) grad[i] = Ma[i] - qs[i] - grad[i];
   SYNC();
   minv();
@@ -2862,14 +2785,7 @@ __device__ __forceinline__ void solve_cg(const Ctx& c, float scale, float tol) {
     stage_count(c, CNT_NEWTON_IT);
     int changed = 0;
     float g0 = 0.f;
-    float alpha;
-    if (jreg) {
-      jdir(dir, c.f(c.L.efc_jv));
-      stage_mark(c, ST_JACVEC);
-      alpha = line_search<false, true, false, true>(c, qacc, Ma, dir, &changed, &g0);
-    } else {
-      alpha = line_search<false, true>(c, qacc, Ma, dir, &changed, &g0);
-    }
+    const float alpha = line_search<false, true>(c, qacc, Ma, dir, &changed, &g0);
     stage_mark(c, ST_NEWTON_LS);
     if (alpha == 0.f) break;
     const float* jvd = c.f(c.L.efc_jv);
@@ -2883,8 +2799,7 @@ __device__ __forceinline__ void solve_cg(const Ctx& c, float scale, float tol) {
     // the decrease along the line, -alpha g0 / 2 (exact for a quadratic segment): the
     // difference of two fp32 costs drowns in rounding long before CG's slow tail ends
     const float impr = -0.5f * scale * alpha * g0;
-    if (jreg) jtf(grad);
-    else jac_t_force(c, grad);
+    jac_t_force(c, grad);
     float gn = 0;
     for (int i = LANE; i < nv; i += DX_WAVE) {
       grad[i] = Ma[i] - qs[i] - grad[i];
@@ -3161,15 +3076,6 @@ __device__ __forceinline__ void solve_pgs_ar(const Ctx& c, float scale, float to
     const float wd = __int_as_float(__builtin_amdgcn_ds_bpermute(8 * (LANE & 31), __float_as_int(r)));
     wl = (LANE < nv ? wd : 0.f) + wt;
   };
-  auto dotw = [&](const float (&p)[30]) {
-    float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-    for (int d = 0; d < 30; d += 2) {
-      s0 = fmaf(p[d], rl(wl, d), s0);
-      s1 = fmaf(p[d + 1], rl(wl, d + 1), s1);
-    }
-    return s0 + s1;
-  };
   // one row update, in the row's lane q (q static: a register name of A[B]).  The chain
   // from one row to the next is med3 -> readlane -> fma.  A lane's box (lof, hif) changes
   // only at its own row, which a sweep visits once, so the row's change is kept (dsv) and
@@ -3197,7 +3103,7 @@ __device__ __forceinline__ void solve_pgs_ar(const Ctx& c, float scale, float to
         // newton_linesearch, the formation above as newton_hessian)
         if (nb > 1 || ntail > 0 || it == 0) {  // (one block alone keeps its residuals current)
           wsum();
-          res[B] = (dotw(P[B]) + bb[B] + rk[B] * (lob[B] - lof[B])) * idg[B];
+          res[B] = (mrow_dot(P[B], wl) + bb[B] + rk[B] * (lob[B] - lof[B])) * idg[B];
           stage_mark(c, ST_NEWTON_GRAD);
         }
         float df = 0.f;  // this lane's row's force change in the sweep
@@ -3272,6 +3178,25 @@ __device__ __forceinline__ void solve_pgs_ar(const Ctx& c, float scale, float to
   if (LANE == 0) c.I[I_NITER] = it;
   SYNC();
 }
+// A serial sweep's row update: the force fo less res / AR_rr, projected on the row's box
+// ([-floss, floss] on a friction-loss row, [0, inf) on every other); *dl is its change.
+__device__ __forceinline__ float pgs_project(int type, float floss, float fo, float ar, float res, float* dl) {
+  float fn = fo - res / ar;
+  fn = type == DXR_FRIC ? fminf(floss, fmaxf(-floss, fn)) : fmaxf(fn, 0.f);
+  *dl = fn - fo;
+  return fn;
+}
+// The serial sweeps' ending: the forces f go back as residuals whose primal force is f_r,
+// and the sweep count.  (solve_pgs_ar ends otherwise: its blocks' forces are in registers.)
+template <class Ctx>
+__device__ __forceinline__ void pgs_store_forces(const Ctx& c, const float* f, int it) {
+  const int nefc = c.I[I_NEFC];
+  float* jar = c.f(c.L.efc_jar);
+  const float* D = c.f(c.L.efc_D);
+  for (int r = LANE; r < nefc; r += DX_WAVE) jar[r] = -f[r] / D[r];
+  if (LANE == 0) c.I[I_NITER] = it;
+  SYNC();
+}
 // [3P] MuJoCo's PGS (mj_solPGS), <option solver="PGS">: projected Gauss-Seidel on the
 // dual, min_f 0.5 f'(A + R) f + f'b with A = J M^-1 J' and b = J qacc_smooth - aref;
 // friction-loss rows boxed to +-floss, limit and pyramidal contact rows f >= 0, rows in
@@ -3298,7 +3223,6 @@ __device__ __forceinline__ void solve_pgs(const Ctx& c, float scale, float tol) 
   const int* meta = (const int*)c.f(c.L.efc_meta);
   const float* D = c.f(c.L.efc_D);
   const float* fl = c.f(c.L.efc_fl);
-  const float* Rf = c.f(c.L.efc_Rf);
   const float* aref = c.f(c.L.efc_aref);
   const float* M = c.f(c.L.M);
   float* T = c.f(c.L.H);
@@ -3317,9 +3241,9 @@ __device__ __forceinline__ void solve_pgs(const Ctx& c, float scale, float tol) 
   // warm start: jar holds J qacc_warmstart - aref (solve); g = J'f, u = M^-1 g
   float dc = 0.f;
   for (int r = LANE; r < nefc; r += DX_WAVE) {
-    const bool fr = r < c.nfric;
+    const RowP p = row_params_at(c, r);
     float fo, hw;
-    row_force(meta[r] & 15, D[r], fr ? fl[r] : 0.f, fr ? Rf[r] : 0.f, jar[r], fo, hw);
+    row_force(p.type, p.D, p.fl, p.Rf, jar[r], fo, hw);
     f[r] = fo;
     dc += 0.5f * fo * fo / D[r] - fo * aref[r];
   }
@@ -3344,26 +3268,11 @@ __device__ __forceinline__ void solve_pgs(const Ctx& c, float scale, float tol) 
     // few scalars and, for a changed force, M^-1 J_r' from 30 readlanes -- no LDS round
     // trip on the chain from one row to the next
     float mi[30];
-    const int d = min(LANE, nv - 1);
-#pragma unroll
-    for (int k = 0; k < 30; k++) {
-      const int kc = min(k, nv - 1);
-      const float t = T[ti(max(d, kc)) + min(d, kc)];
-      mi[k] = LANE < nv && k < nv ? t : 0.f;
-    }
+    mrow_load(T, nv, mi);
     float qa = LANE < nv ? qacc[LANE] : 0.f;
-    auto minv_row = [&](float jr) {
-      float u0 = 0.f, u1 = 0.f;
-#pragma unroll
-      for (int k = 0; k < 30; k += 2) {
-        u0 = fmaf(mi[k], rl(jr, k), u0);
-        u1 = fmaf(mi[k + 1], rl(jr, k + 1), u1);
-      }
-      return u0 + u1;
-    };
     for (int r = 0; r < nefc; r++) {
       const float jr = pgs_jrow(c, r);
-      const float sr = wave_sum(jr * minv_row(jr));
+      const float sr = wave_sum(jr * mrow_dot(mi, jr));
       if (LANE == 0) ard[r] = sr + 1.0f / D[r];
     }
     SYNC();
@@ -3376,11 +3285,10 @@ __device__ __forceinline__ void solve_pgs(const Ctx& c, float scale, float tol) 
         const int ty = meta[r] & 15;
         const float fo = f[r], ar = ard[r], ra = aref[r], dr = D[r], fr = ty == DXR_FRIC ? fl[r] : 0.f;
         const float res = wave_sum(jr * qa) - ra + fo / dr;
-        float fn = fo - res / ar;
-        fn = ty == DXR_FRIC ? fminf(fr, fmaxf(-fr, fn)) : fmaxf(fn, 0.f);
-        const float dl = fn - fo;
+        float dl;
+        const float fn = pgs_project(ty, fr, fo, ar, res, &dl);
         if (dl != 0.f) {
-          qa = fmaf(dl, minv_row(jr), qa);
+          qa = fmaf(dl, mrow_dot(mi, jr), qa);
           if (LANE == 0) f[r] = fn;
           impr -= 0.5f * ar * dl * dl + dl * res;
         }
@@ -3389,9 +3297,7 @@ __device__ __forceinline__ void solve_pgs(const Ctx& c, float scale, float tol) 
       if (scale * impr < tol) break;
     }
     if (LANE < nv) qacc[LANE] = qa;
-    for (int r = LANE; r < nefc; r += DX_WAVE) jar[r] = -f[r] / D[r];
-    if (LANE == 0) c.I[I_NITER] = it;
-    SYNC();
+    pgs_store_forces(c, f, it);
     return;
   }
   // AR's diagonal: J_r M^-1 J_r' + R_r
@@ -3409,12 +3315,11 @@ __device__ __forceinline__ void solve_pgs(const Ctx& c, float scale, float tol) 
     for (int r = 0; r < nefc; r++) {
       pgs_row(c, r, Jd);
       const float jq = wave_sum(LANE < nv ? Jd[LANE] * qacc[LANE] : 0.f);
+      const int ty = meta[r] & 15;
       const float fo = f[r], ar = ard[r];
       const float res = jq - aref[r] + fo / D[r];
-      float fn = fo - res / ar;
-      if ((meta[r] & 15) == DXR_FRIC) fn = fminf(fl[r], fmaxf(-fl[r], fn));
-      else fn = fmaxf(fn, 0.f);
-      const float dl = fn - fo;
+      float dl;
+      const float fn = pgs_project(ty, ty == DXR_FRIC ? fl[r] : 0.f, fo, ar, res, &dl);
       if (dl != 0.f) {
         minv(Jd, u);
         if (LANE < nv) qacc[LANE] += dl * u[LANE];
@@ -3426,10 +3331,7 @@ __device__ __forceinline__ void solve_pgs(const Ctx& c, float scale, float tol) 
     it++;
     if (scale * impr < tol) break;
   }
-  // the forces as residuals whose primal force is f_r
-  for (int r = LANE; r < nefc; r += DX_WAVE) jar[r] = -f[r] / D[r];
-  if (LANE == 0) c.I[I_NITER] = it;
-  SYNC();
+  pgs_store_forces(c, f, it);
 }
 
 template <class Ctx>
@@ -3500,6 +3402,7 @@ __device__ __forceinline__ void solve(const Ctx& c) {
   stage_count(c, CNT_SOLVE);
   stage_count(c, CNT_NEFC, nefc);
   if (c.solver == 1) {
+    // CG: nv <= 30 with up to 128 rows in registers (solve_cg_reg), every other size in LDS
     if (DX_SWEEP && nv <= 30 && nefc <= 2 * DX_WAVE) solve_cg_reg(c, scale, tol);
     else solve_cg(c, scale, tol);
     return;
@@ -4291,6 +4194,39 @@ __device__ __forceinline__ float fused_reach_prep(Ctx& c, const DevBatch& B, int
   return env_begin(c, B, env);
 }
 
+// What every driver below does with a context before an env's first stage: the block's
+// integers, the env's separating-direction cache, the narrowphase width and, for a driver
+// that profiles (`prof`), the env's stage accumulators.  The deferral policy (defer,
+// defer_at) is where the drivers differ and stays with them.
+template <class Ctx>
+__device__ __forceinline__ void ctx_bind_env(Ctx& c, const DevBatch& B, int env, bool prof = false) {
+  c.I = (int*)(c.S + c.L.ints);
+  c.sep = B.sepcache ? B.sepcache + (size_t)env * DX_SEP_SLOTS : nullptr;
+  c.np_wide = B.np_wide;
+  if (prof) c.stage_acc = B.stage_acc ? B.stage_acc + (size_t)env * DX_NSTAGE : nullptr;
+}
+
+// The tiers' run of an env they took over: its physics steps s0 .. nsub - 1, up to the end of
+// its control step or to the first one that is deferred (I_DEFER; never with c.defer off).
+// Returns that step, nsub at the end.  (step_body keeps a loop of its own, which also holds
+// its forward-only mode: taking mode 0 out of it changed how the specializations' step
+// kernels unroll the solver, profiles/solver_driver_refactor_census.txt.)
+template <class Ctx>
+__device__ __forceinline__ int env_run_to_end(const Ctx& c, const DevBatch& B, int env, int s0, int nsub, float& time) {
+  int s = s0;
+  for (; s < nsub; s++) {
+    env_substep(c, B, time, env, s == nsub - 1);
+    if (c.I[I_DEFER]) break;
+  }
+  return s;
+}
+// The end of a control step that a tier ran: the outputs and the fused task_post.
+template <class Ctx>
+__device__ __forceinline__ void env_complete(const Ctx& c, const DevBatch& B, int env, float time) {
+  env_finish(c, B, env, time);
+  if (B.fuse) fused_post(c, B, env, false);
+}
+
 // mode 0: nsub x (forward + Euler), then observe;  mode 1: forward only (+observe)
 // mode 2: reach sampling pass (goal rollouts / joint sampling), state out only
 template <class SP>
@@ -4302,10 +4238,8 @@ __device__ __forceinline__ void step_body(const DevModel& m, const DevBatch& B, 
   int env = B.order ? B.order[blockIdx.x] : (int)blockIdx.x;
   const unsigned long long t_start = __builtin_amdgcn_s_memtime();
   if (mode == 2 && !B.ts->need[env]) return;
-  CtxT<SP> c(m, Lrt, smem, nullptr, B.stage_acc ? B.stage_acc + (size_t)env * DX_NSTAGE : nullptr);
-  c.I = (int*)(smem + c.L.ints);
-  c.sep = B.sepcache ? B.sepcache + (size_t)env * DX_SEP_SLOTS : nullptr;
-  c.np_wide = B.np_wide;
+  CtxT<SP> c(m, Lrt, smem, nullptr, nullptr);
+  ctx_bind_env(c, B, env, true);
   c.defer_at = B.defer_at;
   c.defer = !prep && B.defer;  // (the reach sampling pass keeps its pool and cuts it)
   if (prep) {  // reach sampling pass (mode 2): new state only, no outputs
@@ -4376,8 +4310,6 @@ template <class SP>
 __device__ __forceinline__ void step_queue(const DevModel& m, const DevBatch& B, const Lds& Lrt, int nsub) {
   extern __shared__ float smem[];
   CtxT<SP> c(m, Lrt, smem, nullptr, nullptr);
-  c.I = (int*)(smem + c.L.ints);
-  c.np_wide = B.np_wide;
   c.defer_at = B.defer_at;
   c.defer = B.defer != nullptr;
   const int nqueue = B.nqueue;
@@ -4433,8 +4365,7 @@ __device__ __forceinline__ void step_queue(const DevModel& m, const DevBatch& B,
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     const unsigned long long t_start = __builtin_amdgcn_s_memtime();
-    c.stage_acc = B.stage_acc ? B.stage_acc + (size_t)env * DX_NSTAGE : nullptr;
-    c.sep = B.sepcache ? B.sepcache + (size_t)env * DX_SEP_SLOTS : nullptr;
+    ctx_bind_env(c, B, env, true);
     float* rec = B.hand + (size_t)env * B.hand_stride;
     // cost so far (shader cycles / 1024), carried in the record between substeps
     const unsigned cost0 = s > 0 ? __float_as_uint(rec[c.nq + 2 * c.nv + 1]) : 0u;
@@ -4600,13 +4531,10 @@ dx_step_hi_kernel(const DevModel* __restrict__ mp, DevBatch B, Lds L, int nsub) 
     e = __shfl(e, 0, 64);
     const int env = defer_env(e), s0 = defer_step(e);
     CtxT<SpecRT> c(m, L, smem, nullptr, nullptr);
-    c.I = (int*)(smem + c.L.ints);
-    c.sep = B.sepcache ? B.sepcache + (size_t)env * DX_SEP_SLOTS : nullptr;
-    c.np_wide = B.np_wide;
+    ctx_bind_env(c, B, env);
     float time = env_begin(c, B, env, B.hand + (size_t)env * B.hand_stride, true);
-    for (int s = s0; s < nsub; s++) env_substep(c, B, time, env, s == nsub - 1);
-    env_finish(c, B, env, time);
-    if (B.fuse) fused_post(c, B, env, false);
+    env_run_to_end(c, B, env, s0, nsub, time);  // (c.defer is off: to the end)
+    env_complete(c, B, env, time);
     if (LANE == 0) __hip_atomic_fetch_add(B.qdone + 1, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
   }
   int ok = 1;
@@ -4629,9 +4557,7 @@ dx_step_hi_kernel(const DevModel* __restrict__ mp, DevBatch B, Lds L, int nsub) 
     const unsigned e = list[2 + i];
     const int env = defer_env(e), s0 = defer_step(e);
     CtxT<SpecRT> c(m, L, smem, nullptr, nullptr);
-    c.I = (int*)(smem + c.L.ints);
-    c.sep = B.sepcache ? B.sepcache + (size_t)env * DX_SEP_SLOTS : nullptr;
-    c.np_wide = B.np_wide;
+    ctx_bind_env(c, B, env);
     float time = env_begin(c, B, env, nullptr, true);
     if (e & DX_DEFER_FWD) {
       forward(c, B.xfrc);
@@ -4639,9 +4565,8 @@ dx_step_hi_kernel(const DevModel* __restrict__ mp, DevBatch B, Lds L, int nsub) 
       health_check(c, B, env, time, false);
       env_finish(c, B, env, time);
     } else {
-      for (int s = s0; s < nsub; s++) env_substep(c, B, time, env, s == nsub - 1);
-      env_finish(c, B, env, time);
-      if (B.fuse) fused_post(c, B, env, false);
+      env_run_to_end(c, B, env, s0, nsub, time);
+      env_complete(c, B, env, time);
     }
   }
   // 3. the last workgroup to finish resets the launch-to-launch state
@@ -4739,24 +4664,14 @@ dx_step_mid_kernel(const DevModel* __restrict__ mp, DevBatch B, Lds L, int nsub,
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const int env = defer_env(e), s0 = defer_step(e);
     CtxT<SpecRT> c(m, L, smem, nullptr, nullptr);
-    c.I = (int*)(smem + c.L.ints);
-    c.sep = B.sepcache ? B.sepcache + (size_t)env * DX_SEP_SLOTS : nullptr;
-    c.np_wide = B.np_wide;
+    ctx_bind_env(c, B, env);
     c.defer = true;
     c.defer_at = B.mid_defer_at;
     const float* rec = B.hand + (size_t)env * B.hand_stride;
     float time = env_begin(c, B, env, rec, true);
-    int s = s0;
-    for (; s < nsub; s++) {
-      env_substep(c, B, time, env, s == nsub - 1);
-      if (c.I[I_DEFER]) break;
-    }
-    if (s < nsub) {
-      env_defer(c, B, env, s, false, time, B.defer2);
-    } else {
-      env_finish(c, B, env, time);
-      if (B.fuse) fused_post(c, B, env, false);
-    }
+    const int s = env_run_to_end(c, B, env, s0, nsub, time);
+    if (s < nsub) env_defer(c, B, env, s, false, time, B.defer2);
+    else env_complete(c, B, env, time);
     // finished: its stores (and a deferral to the overflow tier's list) before the count
     // the overflow tier waits for
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
