@@ -40,6 +40,7 @@ EXPORTS = (
     "dx_env_step_random", "dx_env_save", "dx_env_load", "dx_env_state_field", "dx_env_step_host",
     "dx_build_key", "dx_env_set_action_filter", "dx_env_action_noise_draw",
     "dx_env_set_hand_observables", "dx_env_hand_obs_dim",
+    "dx_env_set_obs_pipeline", "dx_env_obs_pipe_dims", "dx_env_obs_noise_draw",
 )
 COMM_ID_BYTES = 128
 STAGES = ("kinematics", "crb", "broadphase", "midphase", "narrowphase", "constraints", "velocity",
@@ -57,6 +58,11 @@ ACT_NOISE, ACT_SMOOTH, ACT_PREVIOUS = 1, 2, 4  # dx_action_filter.flags
 OUT_HAND_OBS = 9
 # dx_hand_obs.mask, in the order of the row's blocks within a hand
 HOBS_JOINT_POSITIONS, HOBS_TIP_ORIENTATIONS, HOBS_TIP_ANGULAR_VELOCITIES, HOBS_TIP_POSITIONS_EGO = 1, 2, 4, 8
+OUT_OBS_BUFFER = 10
+# dx_obs_pipeline.padding / .aggregator, by composer's names
+OBS_PAD = {"zero": 0, "initial_value": 1}
+OBS_AGG = {None: 0, "min": 1, "max": 2, "mean": 3, "median": 4, "sum": 5}
+OBS_INTERVAL_MAX, OBS_DELAY_MAX, OBS_BUFFER_MAX = 64, 64, 16  # control steps, control steps, slots
 TASK_REORIENT, TASK_REACH, TASK_HANDOVER = 0, 1, 2
 OBJ_BODY, OBJ_GEOM, OBJ_SITE = 1, 5, 6  # dx_obj_type (MuJoCo's mjtObj values)
 REACH_NPARAMS_HEAD = 26
@@ -102,6 +108,22 @@ class HandObs(ctypes.Structure):
         ("mask", ctypes.c_int32),
         ("nhands", ctypes.c_int32),
         ("root_body", ctypes.c_int32 * 2),
+    ]
+
+
+class ObsPipeline(ctypes.Structure):
+    """struct dx_obs_pipeline (include/dx.h)."""
+
+    _fields_ = [
+        ("update_interval", ctypes.c_int32),
+        ("delay", ctypes.c_int32),
+        ("buffer_size", ctypes.c_int32),
+        ("aggregator", ctypes.c_int32),
+        ("padding", ctypes.c_int32),
+        ("noise", ctypes.c_int32),
+        ("noise_seed", ctypes.c_uint64),
+        ("noise_sigma", ctypes.c_void_p),
+        ("nsigma", ctypes.c_int32),
     ]
 
 
@@ -189,6 +211,10 @@ def load(path: str = LIB_PATH):
     if hasattr(L, "dx_env_set_hand_observables"):  # (an older variant library for A/B lacks the hand observables)
         L.dx_env_set_hand_observables.argtypes = [vp, ctypes.POINTER(HandObs)]
         L.dx_env_hand_obs_dim.argtypes = [vp]
+    if hasattr(L, "dx_env_set_obs_pipeline"):  # (an older variant library for A/B lacks the observation pipeline)
+        L.dx_env_set_obs_pipeline.argtypes = [vp, ctypes.POINTER(ObsPipeline)]
+        L.dx_env_obs_pipe_dims.argtypes = [vp, ctypes.POINTER(i32)]
+        L.dx_env_obs_noise_draw.argtypes = [vp, i32, vp]
     L.dx_timing_enable.argtypes = [vp, ctypes.c_int]
     L.dx_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i32)]
     L.dx_stage_timing.argtypes = [vp, ctypes.c_int]

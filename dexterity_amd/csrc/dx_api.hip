@@ -1808,7 +1808,20 @@ struct dx_env {
   // from before orientations / ego positions switched it on (-1: not switched)
   HandObs H{};
   int hobs_prev_bodies = -1;
+  // the observation pipeline (dx_env_set_obs_pipeline): off while O.on == 0; its buffers
+  // are sized by the configuration, so they are the env's own (obs_pipe_free), allocated
+  // by every accepted call and gone while the pipeline is off
+  ObsPipe O{};
 };
+
+static void obs_pipe_free(ObsPipe& O) {
+  (void)hipFree(O.ring);
+  (void)hipFree(O.count);
+  (void)hipFree(O.mt);
+  (void)hipFree((void*)O.sigma);
+  (void)hipFree(O.out);
+  O = ObsPipe{};
+}
 
 extern "C" dx_env* dx_env_create(const dx_model* m, int32_t nenv, int32_t device, int32_t task,
                                  uint64_t seed, const float* params, int32_t nparams) {
@@ -1972,6 +1985,7 @@ extern "C" int dx_env_goal_dim(const dx_env* e) { return e ? e->P.goal_dim : fai
 
 extern "C" void dx_env_destroy(dx_env* e) {
   if (!e) return;
+  obs_pipe_free(e->O);
   dx_batch_destroy(e->batch);
   delete e;
 }
@@ -1991,6 +2005,16 @@ enum { HOBS_NEEDS_BODIES = DX_HOBS_TIP_ORIENTATIONS | DX_HOBS_TIP_POSITIONS_EGO 
 static int env_hand_obs(dx_env* e) {
   if (!e->H.mask) return 0;
   HIPCHK(dx_launch_hand_obs(e->batch->stream, e->H));
+  return 0;
+}
+// What follows a control step's last launch: the hand observables' gather, then the
+// observation pipeline (dx_obspipe.hip), which reads DX_OUT_OBS, the step type and that
+// gather's rows -- all on the batch stream, so the launch point above orders it too.
+// Nothing is launched while the pipeline is off.
+static int env_observe(dx_env* e) {
+  if (int rc = env_hand_obs(e)) return rc;
+  if (!e->O.on) return 0;
+  HIPCHK(dx_launch_obs_pipe(e->batch->stream, e->O, 0));
   return 0;
 }
 
@@ -2041,7 +2065,7 @@ static int env_run(dx_env* e, const float* action, bool random = false, uint64_t
     B.action = nullptr;
     B.act_random = 0;
     if (rc) return rc;
-    return env_hand_obs(e);
+    return env_observe(e);
   }
   if (random) {  // the random agent into the action buffer, then the step
     void* buf = nullptr;
@@ -2062,7 +2086,7 @@ static int env_run(dx_env* e, const float* action, bool random = false, uint64_t
   if (int rc = launch_step(b, e->nsub, 0)) return rc;
   hipLaunchKernelGGL(dx_task_post_kernel, dim3((e->P.nenv + 3) / 4), dim3(256), 0, b->stream, e->P, e->S, b->db);  // a wave per env
   HIPCHK(hipGetLastError());
-  return env_hand_obs(e);
+  return env_observe(e);
 }
 
 extern "C" int dx_env_reset(dx_env* e) {
@@ -2217,6 +2241,9 @@ extern "C" int dx_env_set_hand_observables(dx_env* e, const dx_hand_obs* cfg) {
   const int all = DX_HOBS_JOINT_POSITIONS | DX_HOBS_TIP_ORIENTATIONS | DX_HOBS_TIP_ANGULAR_VELOCITIES |
                   DX_HOBS_TIP_POSITIONS_EGO;
   if (mask & ~all) return fail(DX_EINVAL, "hand observables: unknown bit in the mask");
+  // the mask sets the width of the observation pipeline's row
+  if (e->O.on)
+    return fail(DX_EINVAL, "hand observables: switch the observation pipeline off first (dx_env_set_obs_pipeline(e, NULL))");
   HandObs& H = e->H;
   const TaskParams& P = e->P;
   const DevModel& d = b->dm;
@@ -2284,6 +2311,103 @@ extern "C" int dx_env_set_hand_observables(dx_env* e, const dx_hand_obs* cfg) {
 extern "C" int dx_env_hand_obs_dim(const dx_env* e) {
   if (!e) return fail(DX_EINVAL, "null env");
   return e->H.mask ? e->H.dim : 0;
+}
+
+// ------------------------------------------------------------------------ //
+// the observation pipeline (dx_obspipe.hip dx_obs_pipe_kernel)
+// ------------------------------------------------------------------------ //
+extern "C" int dx_env_set_obs_pipeline(dx_env* e, const dx_obs_pipeline* p) {
+  if (!e) return fail(DX_EINVAL, "null env");
+  dx_batch* b = e->batch;
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));  // may be called between steps
+  if (!p) {  // off: the step's launches, outputs and checkpoint are those of an env never configured
+    obs_pipe_free(e->O);
+    return 0;
+  }
+  // every check ahead of every change: a rejected call leaves the configuration as it was
+  if (p->update_interval < 1 || p->update_interval > 64)
+    return fail(DX_EINVAL, "observation pipeline: update_interval outside 1..64 control steps");
+  if (p->delay < 0 || p->delay > 64) return fail(DX_EINVAL, "observation pipeline: delay outside 0..64 control steps");
+  if (p->buffer_size < 1 || p->buffer_size > DX_OBSP_KMAX)
+    return fail(DX_EINVAL, "observation pipeline: buffer_size outside 1..16");
+  if (p->aggregator < DX_OBS_AGG_NONE || p->aggregator > DX_OBS_AGG_SUM)
+    return fail(DX_EINVAL, "observation pipeline: unknown aggregator");
+  if (p->padding != DX_OBS_PAD_ZERO && p->padding != DX_OBS_PAD_INITIAL)
+    return fail(DX_EINVAL, "observation pipeline: unknown padding");
+  if (p->noise != 0 && p->noise != 1) return fail(DX_EINVAL, "observation pipeline: noise must be 0 or 1");
+  const int hand_dim = e->H.mask ? e->H.dim : 0;
+  const int W = e->P.obs_dim + hand_dim;
+  if (p->noise) {
+    if (!p->noise_sigma || p->nsigma != W)
+      return fail(DX_EINVAL, "observation pipeline: noise needs one sigma per row element (nsigma = obs_dim + hand_obs_dim)");
+    for (int i = 0; i < W; i++)
+      if (!std::isfinite(p->noise_sigma[i]) || p->noise_sigma[i] < 0.0)
+        return fail(DX_EINVAL, "observation pipeline: every sigma must be finite and non-negative");
+  }
+  const int m = p->update_interval, d = p->delay, K = p->buffer_size;
+  const int S = K + (d + m - 1) / m;
+  if (S > DX_OBSP_SLOTS_MAX) return fail(DX_ELIMIT, "observation pipeline: more than 80 ring slots");
+  if (W > DX_OBSP_WMAX) return fail(DX_ELIMIT, "observation pipeline: a row above 512 floats");
+  ObsPipe A{};
+  A.nenv = e->P.nenv; A.obs_dim = e->P.obs_dim; A.hand_dim = hand_dim;
+  A.W = W; A.Wp = (W + 31) & ~31;
+  A.m = m; A.d = d; A.K = K; A.S = S;
+  A.agg = p->aggregator; A.pad = p->padding; A.noise = p->noise;
+  A.obs = e->S.obs; A.hand = hand_dim ? e->H.out : nullptr; A.step_type = e->S.step_type;
+  const size_t E = e->P.nenv, nout = E * (A.agg ? 1 : K) * W;
+  hipError_t err = hipMalloc((void**)&A.ring, E * S * A.Wp * 4);
+  if (err == hipSuccess) err = hipMalloc((void**)&A.count, E * 4);
+  if (err == hipSuccess) err = hipMalloc((void**)&A.out, nout * 4);
+  if (err == hipSuccess) err = hipMemsetAsync(A.ring, 0, E * S * A.Wp * 4, b->stream);
+  if (err == hipSuccess) err = hipMemsetAsync(A.count, 0, E * 4, b->stream);
+  if (err == hipSuccess && p->noise) {  // env e draws from RandomState(noise_seed + env0 + e)
+    err = hipMalloc((void**)&A.mt, E * DX_MTW_WORDS * 4);
+    if (err == hipSuccess) err = hipMalloc((void**)&A.sigma, (size_t)W * 8);
+    if (err == hipSuccess) err = hipMemcpyAsync((void*)A.sigma, p->noise_sigma, (size_t)W * 8, hipMemcpyHostToDevice, b->stream);
+    if (err == hipSuccess) {
+      hipLaunchKernelGGL(dx_mtw_seed_kernel, dim3((e->P.nenv + 63) / 64), dim3(64), 0, b->stream, e->P.nenv,
+                         p->noise_seed + (uint64_t)e->P.env0, A.mt);
+      err = hipGetLastError();
+    }
+  }
+  // every env's history afresh from its current row: n = 0, s_0 taken (and corrupted), the
+  // buffer left holding that read
+  if (err == hipSuccess) err = dx_launch_obs_pipe(b->stream, A, 1);
+  if (err == hipSuccess) err = hipStreamSynchronize(b->stream);  // (the sigma copy has read the caller's array)
+  if (err != hipSuccess) {
+    obs_pipe_free(A);
+    return fail(err == hipErrorOutOfMemory ? DX_ENOMEM : DX_EHIP, std::string("observation pipeline: ") + hipGetErrorString(err));
+  }
+  obs_pipe_free(e->O);
+  A.on = 1;
+  e->O = A;
+  return 0;
+}
+
+extern "C" int dx_env_obs_pipe_dims(const dx_env* e, int32_t out[3]) {
+  if (!e || !out) return fail(DX_EINVAL, "null argument");
+  out[0] = e->P.obs_dim + (e->H.mask ? e->H.dim : 0);
+  out[1] = !e->O.on ? 0 : e->O.agg ? 1 : e->O.K;
+  out[2] = e->O.on;
+  return 0;
+}
+
+extern "C" int dx_env_obs_noise_draw(dx_env* e, int32_t n, double* out_host) {
+  if (!e || !out_host) return fail(DX_EINVAL, "null argument");
+  if (!e->O.on || !e->O.noise) return fail(DX_EINVAL, "observation noise is not enabled");
+  if (n < 1 || n > DX_WAVE) return fail(DX_EINVAL, "between 1 and 64 normals per call");
+  dx_batch* b = e->batch;
+  HIPCHK(hipSetDevice(b->device));
+  double* dev = nullptr;
+  const size_t bytes = (size_t)e->P.nenv * n * 8;
+  HIPCHK(hipMalloc((void**)&dev, bytes));
+  hipError_t err = dx_launch_obs_noise_draw(b->stream, e->P.nenv, (int)n, e->O.mt, dev);
+  if (err == hipSuccess) err = hipMemcpyAsync(out_host, dev, bytes, hipMemcpyDeviceToHost, b->stream);
+  if (err == hipSuccess) err = hipStreamSynchronize(b->stream);
+  (void)hipFree(dev);
+  if (err != hipSuccess) return fail(DX_EHIP, std::string("observation noise draw: ") + hipGetErrorString(err));
+  return 0;
 }
 
 static int env_params_upload(dx_env* e) {
@@ -2368,6 +2492,13 @@ static std::vector<StateField> env_state_fields(dx_env* e) {
   // the hand observables' rows, while they are on (their configuration is not saved): a
   // loaded env reads what the saved one would have, before its next step rewrites them
   if (e->H.mask) f.push_back({"hand_obs", e->H.out, E * e->H.dim * 4});
+  if (e->O.on) {  // the observation pipeline's state, while it is on (its configuration is not saved)
+    const ObsPipe& O = e->O;
+    f.push_back({"obs_ring", O.ring, E * O.S * O.Wp * 4});
+    f.push_back({"obs_count", O.count, E * 4});
+    if (O.noise) f.push_back({"mt_obs_noise", O.mt, E * DX_MTW_WORDS * 4});
+    f.push_back({"obs_buffer", O.out, E * (O.agg ? 1 : O.K) * O.W * 4});
+  }
   return f;
 }
 
@@ -2440,6 +2571,10 @@ extern "C" int dx_env_output(dx_env* e, int which, void** devptr) {
     case DX_OUT_HAND_OBS:
       if (!e->H.mask) return fail(DX_EINVAL, "no hand observables: dx_env_set_hand_observables has none enabled");
       *devptr = e->H.out;
+      return 0;
+    case DX_OUT_OBS_BUFFER:
+      if (!e->O.on) return fail(DX_EINVAL, "no observation buffer: the observation pipeline is off (dx_env_set_obs_pipeline)");
+      *devptr = e->O.out;
       return 0;
   }
   return fail(DX_EINVAL, "unknown output");

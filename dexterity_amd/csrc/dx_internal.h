@@ -344,6 +344,29 @@ struct HandObs {
   float* out;                    // [nenv][dim]
 };
 
+// The observation pipeline behind the step (dx_env_set_obs_pipeline; dx_obspipe.hip
+// dx_obs_pipe_kernel): composer's per-observable buffer, delay, aggregator and corruptor
+// over the row obs || hand row.  Like the two above, its state belongs to the dx_env: the
+// step kernels never see it, and it never feeds back into them.
+#define DX_OBSP_WAVES 4      // envs (one wave each) per workgroup
+#define DX_OBSP_KMAX 16      // buffer_size
+#define DX_OBSP_SLOTS_MAX 80 // ring slots S = K + ceil(d / m)
+#define DX_OBSP_WMAX 512     // row words a wave's LDS holds (a wider row is DX_ELIMIT)
+struct ObsPipe {
+  int on;                        // 0: off (nothing is launched)
+  int nenv, obs_dim, hand_dim;   // the row: obs_dim floats of DX_OUT_OBS, then hand_dim of DX_OUT_HAND_OBS
+  int W, Wp;                     // row width, and rounded up to 32 words (whole 128-B lines)
+  int m, d, K, S;                // interval, delay (control steps), buffer size, ring slots
+  int agg, pad, noise;           // DX_OBS_AGG_*, DX_OBS_PAD_*, 0 / 1
+  const float *obs, *hand;       // TaskState::obs, HandObs::out (null while hand_dim == 0)
+  const int* step_type;          // TaskState's, read after the step wrote it
+  float* ring;                   // [nenv][S][Wp], sample j of the episode in slot j % S
+  int* count;                    // [nenv] control steps since the episode's FIRST observation
+  uint32_t* mt;                  // [nenv][DX_MTW_WORDS] RandomState(noise_seed + env0 + e); null without noise
+  const double* sigma;           // [W] the noise's stddev per row element; null without noise
+  float* out;                    // DX_OUT_OBS_BUFFER: [nenv][K][W] oldest first, [nenv][W] with an aggregator
+};
+
 // numpy.random.RandomState-compatible MT19937 ([3P] numpy legacy seeding and
 // random_sample: mt19937_seed, mt19937_gen, legacy_double), one stream per env kept in
 // HBM interleaved over the envs -- word k of env e at k * nenv + e (k < 624), the read
@@ -501,3 +524,8 @@ hipError_t dx_launch_dls(int nenv, size_t lds, hipStream_t stream, const DevMode
 
 // dx_observe.hip: the optional hand observables' gather, queued behind the step's launches
 hipError_t dx_launch_hand_obs(hipStream_t stream, const HandObs& H);
+
+// dx_obspipe.hip: the observation pipeline, queued behind the hand observables' gather
+// (restart: every env starts its history afresh from its current row), and its test hook
+hipError_t dx_launch_obs_pipe(hipStream_t stream, const ObsPipe& O, int restart);
+hipError_t dx_launch_obs_noise_draw(hipStream_t stream, int nenv, int n, uint32_t* mt, double* out);

@@ -77,6 +77,98 @@ HAND_EXTRA_OBSERVABLES = collections.OrderedDict((
 HAND_ROOT_BODY = "forearm"  # hand.root_body: shadow_hand_e.py:62, adroit_hand.py:57
 
 
+def _whole_number(name: str, value) -> int:
+    if callable(value):
+        raise ValueError(f"{name}: callables are not supported (composer allows them; the device pipeline "
+                         "takes constants)")
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+        raise ValueError(f"{name} must be an integer, got {value!r}")
+    return int(value)
+
+
+def obs_pipeline_options(n_sub_steps: int, update_interval=None, buffer_size=1, delay=0, aggregator=None,
+                         padding: str = "zero", noise_std=None, widths=None):
+    """Composer's observable options (ObservableSpec, manipulation/shared/observations.py:8-17)
+    in the units of include/dx.h dx_obs_pipeline.  Pure host code: no library, no GPU.
+
+    Composer counts `update_interval` and `delay` in PHYSICS steps; the device has an
+    observation only at control-step boundaries, so both must be multiples of
+    `n_sub_steps` -- except composer's default, interval 1 with buffer 1, which reads the
+    same as interval `n_sub_steps` (`update_interval=None` means that default).  `widths` is
+    the row: an ordered mapping from observable name to its width or its slice of the row.
+    `noise_std` (additive Gaussian noise, one draw per row element and sample) is None for
+    no noise, a float, an array [W], or a dict from observable name to a float or an array
+    of that observable's width; names absent from the dict get 0.
+
+    Returns (m, d, K, aggregator code, padding code, sigma) with m and d in control steps
+    and sigma a float64 [W] array or None.  Raises ValueError with the reason otherwise."""
+    nsub = _whole_number("n_sub_steps", n_sub_steps)
+    if nsub < 1:
+        raise ValueError("n_sub_steps must be at least 1")
+    K = _whole_number("buffer_size", buffer_size)
+    if K < 1:
+        raise ValueError(f"buffer_size must be at least 1, got {K}")
+    if K > _lib.OBS_BUFFER_MAX:
+        raise ValueError(f"buffer_size {K} is above the device limit of {_lib.OBS_BUFFER_MAX}")
+    interval = nsub if update_interval is None else _whole_number("update_interval", update_interval)
+    if interval < 1:
+        raise ValueError(f"update_interval must be at least 1, got {interval}")
+    if interval % nsub == 0:
+        m = interval // nsub
+    elif interval == 1 and K == 1:
+        m = 1  # composer's default: the boundary read returns the boundary's own sample
+    else:
+        raise ValueError(f"update_interval {interval} is not a multiple of n_sub_steps {nsub}: samples inside a "
+                         "control step are not built (only interval 1 with buffer_size 1 is, composer's default)")
+    delay = _whole_number("delay", delay)
+    if delay < 0:
+        raise ValueError(f"delay must not be negative, got {delay}")
+    if delay % nsub:
+        raise ValueError(f"delay {delay} is not a multiple of n_sub_steps {nsub}: arrivals inside a control step "
+                         "are not built")
+    d = delay // nsub
+    if m > _lib.OBS_INTERVAL_MAX or d > _lib.OBS_DELAY_MAX:
+        raise ValueError(f"update_interval / delay of {m} / {d} control steps are above the device limits of "
+                         f"{_lib.OBS_INTERVAL_MAX} / {_lib.OBS_DELAY_MAX}")
+    if callable(aggregator):
+        raise ValueError("aggregator: callables are not supported, name one of min, max, mean, median, sum")
+    if aggregator not in _lib.OBS_AGG:
+        raise ValueError(f"unknown aggregator {aggregator!r}: one of None, min, max, mean, median, sum")
+    pad = padding.lower() if isinstance(padding, str) else padding
+    if pad not in _lib.OBS_PAD:
+        raise ValueError(f"unknown padding {padding!r}: 'zero' or 'initial_value' (composer's ObservationPadding)")
+    slices, W = collections.OrderedDict(), 0
+    for name, w in (widths or {}).items():
+        w = (w.stop - w.start) if isinstance(w, slice) else int(w)
+        slices[name] = slice(W, W + w)
+        W += w
+    sigma = None
+    if noise_std is not None:
+        if callable(noise_std):
+            raise ValueError("noise_std: callables (custom corruptors) are not supported")
+        if isinstance(noise_std, dict):
+            unknown = [k for k in noise_std if k not in slices]
+            if unknown:
+                raise ValueError(f"noise_std names unknown observables {unknown}; the row has {list(slices)}")
+            sigma = np.zeros(W, dtype=np.float64)
+            for name, v in noise_std.items():
+                if callable(v):
+                    raise ValueError(f"noise_std[{name!r}]: callables are not supported")
+                v = np.asarray(v, dtype=np.float64)
+                s = slices[name]
+                if v.ndim > 1 or (v.ndim == 1 and v.size != s.stop - s.start):
+                    raise ValueError(f"noise_std[{name!r}] has {v.size} entries, the observable {s.stop - s.start}")
+                sigma[s] = v
+        else:
+            v = np.asarray(noise_std, dtype=np.float64)
+            if v.ndim > 1 or (v.ndim == 1 and v.size != W):
+                raise ValueError(f"noise_std has {v.size} entries, the row {W}")
+            sigma = np.broadcast_to(v, (W,)).astype(np.float64)
+        if not np.all(np.isfinite(sigma)) or np.any(sigma < 0):
+            raise ValueError("noise_std must be finite and not negative")
+    return m, d, K, _lib.OBS_AGG[aggregator], _lib.OBS_PAD[pad], sigma
+
+
 def observation_layout(hand_nq: int, hand_nv: int, ntips: int, with_prop: bool, hand: str,
                        goal_dim: int = 4) -> "collections.OrderedDict[str, slice]":
     """Named slices of the flat observation vector written by dx_task_post_kernel."""
@@ -409,6 +501,9 @@ class GoalEnvironment:
         self.hand_observables = ()
         self.hand_obs_dim = 0
         self._hand_layout = collections.OrderedDict()
+        # configure_observations' current settings (None: the observation pipeline is off)
+        self.observation_config = None
+        self._obs_pipe = None  # (row width W, delivered rows per env, aggregated)
         if np.isfinite(self.time_limit):
             _lib.check(L.dx_env_set_time_limit(self.ptr, self.time_limit))
         # max_time_per_goal in fp64 (the params carry it as a float)
@@ -443,6 +538,9 @@ class GoalEnvironment:
 
     def observation_spec(self) -> "collections.OrderedDict[str, Array]":
         lead = () if self.strip_singleton_obs_buffer_dim else (1,)
+        if self._obs_pipe is not None:  # composer: (buffer_size, n), no buffer axis behind an aggregator
+            _, rows, aggregated = self._obs_pipe
+            lead = () if aggregated or (rows == 1 and self.strip_singleton_obs_buffer_dim) else (rows,)
         return collections.OrderedDict(
             (k, Array(lead + (s.stop - s.start,), np.float64, name=k))
             for k, s in list(self._layout.items()) + list(self._hand_layout.items())
@@ -482,6 +580,8 @@ class GoalEnvironment:
         np.copyto(self._pin_act, a)
         _lib.check(L.dx_env_step_host(self.ptr, self._pin_act.ctypes.data, self._pin_out.ctypes.data))
         ts = self._timestep_packed(self._pin_out)
+        if self._obs_pipe is not None:  # the packed row keeps the raw observation: one more copy
+            return ts._replace(observation=self._pipeline_observation())
         if self.hand_obs_dim:  # the packed row does not carry them: one more copy
             ts.observation.update(self._hand_observation())
         return ts
@@ -590,6 +690,75 @@ class GoalEnvironment:
         """[num_envs, hand_obs_dim] float32 host copy of the rows (DxError while off)."""
         return self._read(_lib.OUT_HAND_OBS, np.float32, self.hand_obs_dim)
 
+    # ---------------------------------------------------------------- observation pipeline
+    def _row_layout(self) -> "collections.OrderedDict[str, slice]":
+        """Named slices of the pipeline's row: the observation, then the hand observables."""
+        out = collections.OrderedDict(self._layout)
+        for k, s in self._hand_layout.items():
+            out[k] = slice(self.obs_dim + s.start, self.obs_dim + s.stop)
+        return out
+
+    def configure_observations(self, update_interval: Optional[int] = None, buffer_size: int = 1, delay: int = 0,
+                               aggregator: Optional[str] = None, padding: str = "zero", noise_std=None,
+                               noise_seed: Optional[int] = None) -> None:
+        """Composer's observable options on the device, behind every control step (include/dx.h
+        dx_env_set_obs_pipeline): `update_interval` and `delay` in PHYSICS steps as composer
+        counts them (multiples of the task's n_sub_steps; `obs_pipeline_options` has the
+        rule), `buffer_size`, `aggregator` (None, "min", "max", "mean", "median", "sum"),
+        `padding` ("zero" or "initial_value": composer's delayed_observation_padding) and
+        `noise_std`, additive Gaussian noise per sample (a float, an array over the row, or a
+        dict by observable name), env e drawing from RandomState(noise_seed + env_offset + e),
+        `noise_seed` defaulting to the env's seed.  One option set covers every observable,
+        the enabled hand observables included -- enable those first: the library refuses to
+        change them while the pipeline is on.  Every TimeStep's observation[name] is then
+        [B, buffer_size, n], or [B, n] with an aggregator or with buffer_size 1 under
+        strip_singleton_obs_buffer_dim, and `observation_spec()` says the same.  Calling this
+        starts every env's history afresh from its current observation; with all defaults
+        it switches the pipeline off.  A checkpoint carries the pipeline's state but not
+        these settings: load it into an env configured the same way."""
+        L = _lib.load()
+        args = dict(update_interval=update_interval, buffer_size=buffer_size, delay=delay, aggregator=aggregator,
+                    padding=padding, noise_std=noise_std)
+        layout = self._row_layout()
+        m, d, K, agg, pad, sigma = obs_pipeline_options(self.task.config.n_sub_steps, widths=layout, **args)
+        if (update_interval is None and (m, d, K, agg) == (1, 0, 1, 0) and sigma is None
+                and pad == _lib.OBS_PAD["zero"]):
+            _lib.check(L.dx_env_set_obs_pipeline(self.ptr, None))
+            self.observation_config = self._obs_pipe = None
+            return
+        p = _lib.ObsPipeline(update_interval=m, delay=d, buffer_size=K, aggregator=agg, padding=pad)
+        if sigma is not None:
+            sigma = np.ascontiguousarray(sigma, dtype=np.float64)
+            p.noise = 1
+            p.noise_seed = int(self._seed if noise_seed is None else noise_seed) & (2**64 - 1)
+            p.noise_sigma = sigma.ctypes.data
+            p.nsigma = sigma.size
+        _lib.check(L.dx_env_set_obs_pipeline(self.ptr, ctypes.byref(p)))
+        dims = (ctypes.c_int32 * 3)()
+        _lib.check(L.dx_env_obs_pipe_dims(self.ptr, dims))
+        assert dims[0] == self.obs_dim + self.hand_obs_dim and dims[2] == 1, list(dims)
+        self._obs_pipe = (int(dims[0]), int(dims[1]), agg != 0)
+        self.observation_config = dict(args, noise_seed=noise_seed)
+
+    def obs_buffer_ptr(self) -> int:
+        """Device address of DX_OUT_OBS_BUFFER: [num_envs, buffer_size, W] float32 oldest first,
+        [num_envs, W] with an aggregator (DxError while the pipeline is off)."""
+        return self._out(_lib.OUT_OBS_BUFFER)
+
+    def obs_buffer(self) -> np.ndarray:
+        """[num_envs, rows, W] float32 host copy of DX_OUT_OBS_BUFFER (rows = 1 with an aggregator)."""
+        if self._obs_pipe is None:
+            raise _lib.DxError("the observation pipeline is off (configure_observations)")
+        W, rows, _ = self._obs_pipe
+        return self._read(_lib.OUT_OBS_BUFFER, np.float32, rows * W).reshape(self.num_envs, rows, W)
+
+    def _pipeline_observation(self) -> "collections.OrderedDict[str, np.ndarray]":
+        _, rows, aggregated = self._obs_pipe
+        buf = self.obs_buffer()
+        flat = aggregated or (rows == 1 and self.strip_singleton_obs_buffer_dim)
+        return collections.OrderedDict(
+            (k, (buf[:, 0, s] if flat else buf[:, :, s]).astype(np.float64)) for k, s in self._row_layout().items())
+
     # ---------------------------------------------------------------- checkpoint
     # dtype of the state fields that are not float32 (include/dx.h dx_env_save)
     _STATE_DTYPES = {"nstep": np.int32, "diverged": np.int32, "successes": np.int32, "counter": np.int32,
@@ -598,7 +767,8 @@ class GoalEnvironment:
                      "goalfail": np.int32, "time_d": np.float64, "solve_start_d": np.float64,
                      "nsub_d": np.int32, "solve_n": np.int32, "mt_env": np.uint32, "mt_goal": np.uint32,
                      "mt_reach": np.uint32, "step_cost": np.uint32, "order": np.int32,
-                     "act_ema_set": np.int32, "mt_noise": np.uint32}
+                     "act_ema_set": np.int32, "mt_noise": np.uint32,
+                     "obs_count": np.int32, "mt_obs_noise": np.uint32}
 
     def _state_fields(self):
         L = _lib.load()
@@ -650,6 +820,10 @@ class GoalEnvironment:
             if ("hand_obs" in z.files) != ("hand_obs" in {name for name, _, _ in fields}):
                 raise ValueError("checkpoint and env differ in the hand observables (on in one, off in the other): "
                                  "enable_observables as the saved env did, then load")
+            for key in ("obs_ring", "mt_obs_noise"):
+                if (key in z.files) != (key in {name for name, _, _ in fields}):
+                    raise ValueError("checkpoint and env differ in the observation pipeline (on in one, off in the "
+                                     "other, or its noise): configure_observations as the saved env did, then load")
             nbytes = sum(nb for _, _, nb in fields)
             buf = np.empty(nbytes, dtype=np.uint8)
             for name, off, nb in fields:
@@ -678,7 +852,10 @@ class GoalEnvironment:
             (k, obs[:, s].astype(np.float64) if self.strip_singleton_obs_buffer_dim
              else obs[:, None, s].astype(np.float64)) for k, s in self._layout.items()
         )
-        observation.update(self._hand_observation())
+        if self._obs_pipe is not None:
+            observation = self._pipeline_observation()
+        else:
+            observation.update(self._hand_observation())
         return TimeStep(st.astype(np.int32), rew, disc, observation)
 
     def goals(self) -> np.ndarray:
@@ -776,4 +953,4 @@ def load(domain_name: str, task_name: str, seed: Optional[int] = None,
 
 
 __all__ = ["load", "GoalEnvironment", "ReOrient", "ReOrientConfig", "Reach", "ReachConfig", "ALL_TASKS",
-           "ALL_NAMES", "TASKS_BY_DOMAIN", "StepType", "HAND_EXTRA_OBSERVABLES"]
+           "ALL_NAMES", "TASKS_BY_DOMAIN", "StepType", "HAND_EXTRA_OBSERVABLES", "obs_pipeline_options"]

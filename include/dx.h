@@ -238,7 +238,10 @@ enum dx_env_out { DX_OUT_OBS = 0, DX_OUT_REWARD = 1, DX_OUT_DISCOUNT = 2, DX_OUT
                   DX_OUT_PREV_ACTION = 8 /* [nenv][nu] f32, PreviousAction.previous_action; once the
                                             action pipeline has been configured (below) */,
                   DX_OUT_HAND_OBS = 9 /* [nenv][dx_env_hand_obs_dim] f32, the optional hand
-                                         observables; while they are on (below) */ };
+                                         observables; while they are on (below) */,
+                  DX_OUT_OBS_BUFFER = 10 /* [nenv][K][W] f32 oldest first, or [nenv][W] with an
+                                            aggregator: the observation pipeline's delivered rows;
+                                            while it is on (below) */ };
 dx_env* dx_env_create(const dx_model* m, int32_t nenv, int32_t device, int32_t task, uint64_t seed,
                       const float* params, int32_t nparams);
 /* One shard of a job's environments: this handle's env e is the job's env env0 + e.
@@ -366,6 +369,75 @@ typedef struct dx_hand_obs {
 int dx_env_set_hand_observables(dx_env* e, const dx_hand_obs* cfg);
 /* Row width of DX_OUT_HAND_OBS; 0 while the feature is off. */
 int dx_env_hand_obs_dim(const dx_env* e);
+
+/* The observation pipeline: the options the reference gives every observable
+ * (ObservableSpec, manipulation/shared/observations.py:8-17, handed on by make_options
+ * :114-120) -- update_interval, buffer_size, delay, aggregator, corruptor -- as composer's
+ * observation updater applies them ([3P] dm_control composer observation updater / buffer),
+ * on the device: one small kernel behind every call that produces DX_OUT_OBS (dx_env_reset,
+ * dx_env_step, dx_env_step_random, dx_env_step_host), behind the hand observables' gather.
+ * The row it works on is DX_OUT_OBS followed, while the hand observables are on, by
+ * DX_OUT_HAND_OBS: W = dx_env_obs_dim + dx_env_hand_obs_dim floats.  One option set applies
+ * to the whole row; noise_sigma is per element.
+ * All times are CONTROL steps (composer counts physics steps: divide by n_sub_steps; only
+ * multiples can be expressed, dexterity_amd.manipulation.obs_pipeline_options does it).
+ * Per env, with n = control steps since the episode's FIRST observation (FIRST: n = 0),
+ * m = update_interval, d = delay, K = buffer_size:
+ *  - sample s_j is taken when n == j m; s_0 is the FIRST observation (the updater's reset
+ *    inserts at time 0); it arrives at j m + d;
+ *  - the corruptor runs once per sample and the buffer keeps the corrupted value:
+ *    float32(double(o_i) + noise_sigma[i] * g_i), the product and the sum in fp64 without
+ *    contraction, g the next W standard normals, in element order, of the env's own
+ *    numpy-compatible RandomState(noise_seed + env0 + e) (legacy polar gaussians; the cached
+ *    second value carries from sample to sample; a zero sigma still consumes its draw; a step
+ *    that takes no sample draws nothing).  The stream of its own is the stated deviation of
+ *    the action noise above, for the same reasons;
+ *  - the read at n: J = floor((n - d) / m) for n >= d, else -1; delivered slot k (0 oldest,
+ *    K-1 newest) is s_{J - (K-1-k)}; a negative index is padding -- zeros (DX_OBS_PAD_ZERO,
+ *    composer's default) or s_0 (DX_OBS_PAD_INITIAL), also while s_0 has not arrived;
+ *  - the aggregator, over the K delivered slots, padding included, in fp64 (the reference's
+ *    rows are float64) rounded to fp32 once: the sum in slot order, oldest first; mean = sum
+ *    / K; the median of an even K is (a + b) * 0.5;
+ *  - dx_env_reset and the step that returns FIRST for an auto-reset env restart the env's
+ *    history (n = 0, s_0 from that FIRST observation); LAST is an ordinary step.
+ * DX_OUT_OBS_BUFFER is a library-owned buffer, [nenv][K][W] oldest first or [nenv][W] with
+ * an aggregator.  Nothing else changes: DX_OUT_OBS, reward, discount, step type, goal, the
+ * packed rows, dx_env_step_host's row and the all-gather keep their values and widths; the
+ * pipeline never feeds back.
+ * dx_env_set_obs_pipeline may be called between steps (it synchronises the stream).  NULL
+ * switches the pipeline off (the default): a control step's launches, every output and the
+ * checkpoint are then those of an env never configured, and dx_env_output(DX_OUT_OBS_BUFFER)
+ * fails.  Switching it on, or reconfiguring it, starts every env's history afresh: n = 0,
+ * s_0 = the env's current row, DX_OUT_OBS_BUFFER left holding that read, the noise streams
+ * seeded again.  A rejected call leaves the configuration and the buffer as they were.
+ * While the pipeline is on dx_env_set_hand_observables fails (DX_EINVAL): the mask sets W;
+ * switch the pipeline off, change the mask, configure the pipeline again.
+ * DX_EINVAL: a field outside its range, an unknown enum, noise other than 0 / 1, noise with
+ * nsigma != W or a null, negative or non-finite sigma.  DX_ELIMIT: more than 80 ring slots
+ * S = K + ceil(d / m) (the field ranges already keep S <= 80), or a row above 512 floats.
+ * While the pipeline is on the checkpoint carries its state after the other fields --
+ * obs_ring, obs_count (int32), mt_obs_noise (with numpy's has_gauss / gauss; while noise is
+ * on), obs_buffer -- but not this configuration: load into an env configured the same way. */
+enum { DX_OBS_PAD_ZERO = 0, DX_OBS_PAD_INITIAL = 1 };
+enum { DX_OBS_AGG_NONE = 0, DX_OBS_AGG_MIN, DX_OBS_AGG_MAX, DX_OBS_AGG_MEAN, DX_OBS_AGG_MEDIAN, DX_OBS_AGG_SUM };
+typedef struct dx_obs_pipeline {
+  int32_t update_interval;   /* m, control steps, 1..64 */
+  int32_t delay;             /* d, control steps, 0..64 */
+  int32_t buffer_size;       /* K, 1..16 */
+  int32_t aggregator;        /* DX_OBS_AGG_* */
+  int32_t padding;           /* DX_OBS_PAD_* */
+  int32_t noise;             /* 0 / 1 */
+  uint64_t noise_seed;
+  const double* noise_sigma; /* host, [W] when noise, else ignored */
+  int32_t nsigma;            /* must equal W when noise */
+} dx_obs_pipeline;
+int dx_env_set_obs_pipeline(dx_env* e, const dx_obs_pipeline* p);
+/* out = { W of the current row, delivered rows per env (K; 1 with an aggregator; 0 while
+ * off), 1 on / 0 off }. */
+int dx_env_obs_pipe_dims(const dx_env* e, int32_t out[3]);
+/* Test hook: the next n (1..64) standard normals of every env's observation-noise stream,
+ * consumed; out_host [nenv][n] f64.  The pipeline must be on with noise. */
+int dx_env_obs_noise_draw(dx_env* e, int32_t n, double* out_host);
 
 /* Checkpoint / resume.  An env's state is the set of device arrays that carry from one
  * control step to the next (physics and task state, the numpy-compatible MT19937 streams,
