@@ -1,7 +1,7 @@
 // dx_device.h -- device toolkit shared by the step kernel (dx_step.hip) and the
 // kinematic-query / inverse-kinematics kernels (dx_ik.hip): wave primitives, small
 // 3D / spatial algebra, the per-env context, the tree passes (kinematics, com
-// positions, tendons, CRB) and the wave / matrix-core Cholesky solvers.
+// positions, tendons, CRB) and the matrix-core Cholesky / sweep solvers.
 #pragma once
 #include "dx_internal.h"
 
@@ -732,49 +732,6 @@ __device__ __forceinline__ void crb_mass(const Ctx& c) {
 
 #undef DX_LANE_GROUP
 #define DX_LANE_GROUP DX_LG_SOLVER
-// In-place dense Cholesky (lower, row-major) of the n x n matrix A, one wave.
-// Column k: lanes scale the sub-diagonal of column k, then update the trailing
-// lower triangle; entry t of a w x w trailing triangle maps to (ii, jj) through
-// the LDS table tri[t] = ii << 8 | jj (built once per launch), so the update is
-// branch-free and balanced over the 64 lanes.  Two barriers per column.
-__device__ __forceinline__ void wave_cholesky(float* A, int n, const unsigned short* tri) {
-  for (int k = 0; k < n; k++) {
-    float d = sqrtf(fmaxf(A[ti(k) + k], 1e-30f));
-    float inv = 1.0f / d;
-    for (int i = k + 1 + LANE; i < n; i += DX_WAVE) A[ti(i) + k] *= inv;
-    SYNC();
-    if (LANE == 0) A[ti(k) + k] = d;
-    int w = n - k - 1;
-    int tot = w * (w + 1) / 2;
-    for (int t = LANE; t < tot; t += DX_WAVE) {
-      int e = tri[t];
-      int i = k + 1 + (e >> 8), j = k + 1 + (e & 255);
-      A[ti(i) + j] -= A[ti(i) + k] * A[ti(j) + k];
-    }
-    SYNC();
-  }
-}
-// Solve (L L^T) x = b; x holds b on entry (LDS).  Lane i keeps x_i in a register;
-// the dependent chain uses readlane broadcasts and no barriers.  n <= 64.
-__device__ __forceinline__ void wave_chol_solve(const float* A, float* x, int n) {
-  float xi = LANE < n ? x[LANE] : 0.f;
-  for (int k = 0; k < n; k++) {
-    float lik = LANE > k && LANE < n ? A[ti(LANE) + k] : 0.f;
-    float v = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(xi), k)) / A[ti(k) + k];
-    if (LANE == k) xi = v;
-    xi -= lik * v;
-  }
-  for (int k = n - 1; k >= 0; k--) {
-    float lki = LANE < k ? A[ti(k) + LANE] : 0.f;
-    float v = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(xi), k)) / A[ti(k) + k];
-    if (LANE == k) xi = v;
-    xi -= lki * v;
-  }
-  SYNC();
-  if (LANE < n) x[LANE] = xi;
-  SYNC();
-}
-
 // Cholesky solve for n <= 32 on the matrix cores.  The matrix, padded to 32 x 32 with
 // an identity block, lives in the 16 accumulator VGPRs of v_mfma_f32_32x32x2_f32
 // (lane l, VGPR v holds C[8 (v/4) + 4 (l/32) + v%4][l%32]; probe:
