@@ -26,7 +26,7 @@ SOURCES = ("dx_step.hip", "dx_ik.hip", "dx_dls.hip", "dx_task.hip", "dx_sensor.h
 HEADERS = ("dx_internal.h", "dx_device.h", "dx_jac.h", "dx_task.h", "dx_mtw.h")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 DIMS = ("nq", "nv", "nbody", "njnt", "nu", "ntendon", "nsite", "nlevel", "nroot", "nfric", "nlimj", "nlimt",
-        "nbpair", "any_damping", "disable_contact", "iterations", "solver")  # dx_device.h DX_DIMS
+        "nbpair", "any_damping", "disable_contact", "iterations", "solver", "solimp_pow2")  # dx_device.h DX_DIMS
 
 
 def _stale() -> bool:

@@ -716,6 +716,17 @@ extern "C" dx_model* dx_model_load(const void* blob, size_t nbytes) {
   d.any_damping = 0;
   for (int i = 0; i < nv; i++)
     if (damp[i] > 0) d.any_damping = 1;
+  // the impedance's power: 2 on every row the model can build?  (each table is [n][5],
+  // power last; the geom pairs' solimp is the mixed one)
+  d.solimp_pow2 = 1;
+  const std::pair<const char*, int> solimp_tabs[] = {
+      {"dof_solimp", nv}, {"jnt_solimp", d.njnt}, {"tendon_solimp", d.ntendon}, {"gpair_solimp", d.ngpair}};
+  for (const auto& tab : solimp_tabs) {
+    const auto it = m->hf.find(tab.first);
+    if (it == m->hf.end()) continue;
+    for (int i = 0; i < tab.second && 5 * i + 4 < (int)it->second.size(); i++)
+      if (it->second[5 * i + 4] != 2.0f) d.solimp_pow2 = 0;
+  }
   // LDS layout (4-byte words).  Persistent arrays first, then a union whose
   // contents change with the stage (dx_step.hip forward()):
   //   A  kinematic block      xpos xmat xipos rcom cdof   kinematics .. make_constraint
@@ -895,17 +906,18 @@ extern "C" int dx_hull_support(const dx_model* m, int32_t mesh, const float dir[
 }
 
 // Layout export for build.py's kernel specialization: the Lds struct (words, in
-// declaration order) followed by the 17 dimensions of dx_device.h DX_DIMS.
+// declaration order) followed by the 18 dimensions of dx_device.h DX_DIMS.
 extern "C" int dx_model_layout(const dx_model* m, int32_t* out, int32_t n) {
   if (!m || !out) return fail(DX_EINVAL, "null argument");
   const int nl = (int)(sizeof(Lds) / sizeof(int));
   const DevModel& d = m->dm;
-  int dims[17] = {d.nq, d.nv, d.nbody, d.njnt, d.nu, d.ntendon, d.nsite, d.nlevel, d.nroot,
-                  d.nfric, d.nlimj, d.nlimt, d.nbpair, d.any_damping, d.disable_contact, d.iterations, d.solver};
-  if (n < nl + 17) return fail(DX_EINVAL, "output too small");
+  int dims[18] = {d.nq, d.nv, d.nbody, d.njnt, d.nu, d.ntendon, d.nsite, d.nlevel, d.nroot,
+                  d.nfric, d.nlimj, d.nlimt, d.nbpair, d.any_damping, d.disable_contact, d.iterations, d.solver,
+                  d.solimp_pow2};
+  if (n < nl + 18) return fail(DX_EINVAL, "output too small");
   memcpy(out, &m->lds, sizeof(Lds));
   memcpy(out + nl, dims, sizeof(dims));
-  return nl + 17;
+  return nl + 18;
 }
 
 extern "C" int dx_model_lds_bytes(const dx_model* m) {

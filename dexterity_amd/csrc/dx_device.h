@@ -246,7 +246,8 @@ __device__ __forceinline__ float dot6(const float* a, const float* b) {
 // bounds are constants, and far fewer scalar registers stay live (the generic
 // kernel spills its ~60 layout/dimension scalars into VGPR lanes).
 #define DX_DIMS(X) X(nq) X(nv) X(nbody) X(njnt) X(nu) X(ntendon) X(nsite) X(nlevel) X(nroot) \
-  X(nfric) X(nlimj) X(nlimt) X(nbpair) X(any_damping) X(disable_contact) X(iterations) X(solver)
+  X(nfric) X(nlimj) X(nlimt) X(nbpair) X(any_damping) X(disable_contact) X(iterations) X(solver) \
+  X(solimp_pow2)
 struct SpecRT {
   static constexpr bool reach_task = false;  // (the generic kernel: no fused reach sampling pass)
 };

@@ -80,6 +80,9 @@ struct DevModel {
   int nq, nv, nbody, njnt, ngeom, nsite, nu, ntendon, nwrap, nbpair, ngpair;
   int iterations, disable_contact, any_damping, nlevel, nroot, nfric, nlimj, nlimt;
   int solver;  // [3P] mjtSolver: 0 PGS, 1 CG, 2 Newton (default)
+  // every solimp a constraint row can take (dof, joint, tendon, mixed geom pair) has MuJoCo's
+  // default power 2: the impedance is its closed form (dx_step.hip impedance)
+  int solimp_pow2;
   float timestep, tolerance, impratio, meaninertia;
   float gravity[3];
   // bodies

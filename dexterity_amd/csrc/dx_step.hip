@@ -771,18 +771,10 @@ __device__ __forceinline__ bool sphere_overlap(const float* c1, float r1, const 
   return dot3(t, t) <= rr * rr;
 }
 
-// Separating-axis test of two oriented boxes (Gottschalk's 15 axes), inflated by margin.
-// obb: [centre(3) in body frame, R(9) body<-box, half extents(3)].
-__device__ __forceinline__ bool obb_overlap(const float* o1, const float* xp1, const float* xm1, const float* o2,
-                            const float* xp2, const float* xm2, float margin) {
-  float ca[3], cb[3], Ra[9], Rb[9];
-  matvec3(ca, xm1, o1);
-  matvec3(cb, xm2, o2);
-  for (int k = 0; k < 3; k++) { ca[k] += xp1[k]; cb[k] += xp2[k]; }
-  matmul3(Ra, xm1, o1 + 3);
-  matmul3(Rb, xm2, o2 + 3);
-  const float* ea = o1 + 12;
-  const float* eb = o2 + 12;
+// Separating-axis test of two oriented boxes (Gottschalk's 15 axes), inflated by margin:
+// world centres ca / cb, rotations world<-box Ra / Rb, half extents ea / eb.
+__device__ __forceinline__ bool sat_overlap(const float* ca, const float* Ra, const float* ea, const float* cb,
+                                            const float* Rb, const float* eb, float margin) {
   float t0[3] = {cb[0] - ca[0], cb[1] - ca[1], cb[2] - ca[2]};
   float t[3], R[9], AR[9];
   // t in a's frame, R = Ra^T Rb
@@ -815,14 +807,30 @@ __device__ __forceinline__ bool obb_overlap(const float* o1, const float* xp1, c
   return true;
 }
 
+// obb: [centre(3) in body frame, R(9) body<-box, half extents(3)], on a body at (xp, xm).
+__device__ __forceinline__ bool obb_overlap(const float* o1, const float* xp1, const float* xm1, const float* o2,
+                            const float* xp2, const float* xm2, float margin) {
+  float ca[3], cb[3], Ra[9], Rb[9];
+  matvec3(ca, xm1, o1);
+  matvec3(cb, xm2, o2);
+  for (int k = 0; k < 3; k++) { ca[k] += xp1[k]; cb[k] += xp2[k]; }
+  matmul3(Ra, xm1, o1 + 3);
+  matmul3(Rb, xm2, o2 + 3);
+  return sat_overlap(ca, Ra, o1 + 12, cb, Rb, o2 + 12, margin);
+}
+
 // Overlap of two boxes given in their bodies' frames (axes = body axes): centre c,
-// half extents e, body pose (xp, xm); the 15-axis SAT of obb_overlap.
+// half extents e, body pose (xp, xm).  The body matrices are the boxes' rotations as they
+// stand: their product with the identity (x*1 + y*0 + z*0) is x up to the sign of a zero,
+// which no inequality of the test can see.
 __device__ __forceinline__ bool box_overlap(const float* c1, const float* e1, const float* xp1, const float* xm1,
                                             const float* c2, const float* e2, const float* xp2, const float* xm2,
                                             float margin) {
-  const float o1[15] = {c1[0], c1[1], c1[2], 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, e1[0], e1[1], e1[2]};
-  const float o2[15] = {c2[0], c2[1], c2[2], 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, e2[0], e2[1], e2[2]};
-  return obb_overlap(o1, xp1, xm1, o2, xp2, xm2, margin);
+  float ca[3], cb[3];
+  matvec3(ca, xm1, c1);
+  matvec3(cb, xm2, c2);
+  for (int k = 0; k < 3; k++) { ca[k] += xp1[k]; cb[k] += xp2[k]; }
+  return sat_overlap(ca, xm1, e1, cb, xm2, e2, margin);
 }
 
 // Appends one contact record (called by a single lane).
@@ -1432,7 +1440,14 @@ __device__ __forceinline__ void collision(const Ctx& c, int watch_only, int wg, 
 // ------------------------------------------------------------------------ //
 // constraints
 // ------------------------------------------------------------------------ //
-__device__ __forceinline__ float impedance(const float* solimp, float violation) {
+// the impedance curve's closed form for MuJoCo's default power 2
+__device__ __forceinline__ float impedance_pow2(float x, float mid) {
+  return x <= mid ? x * x / mid : 1 - (1 - x) * (1 - x) / (1 - mid);
+}
+
+// pow2: every solimp of the model has power 2 (DevModel::solimp_pow2; a constant of a scene
+// specialization), so the kernel carries neither the ladder on the power nor its powf.
+__device__ __forceinline__ float impedance(const float* solimp, float violation, bool pow2) {
   float d0 = fminf(0.9999f, fmaxf(0.0001f, solimp[0]));
   float dmax = fminf(0.9999f, fmaxf(0.0001f, solimp[1]));
   float width = solimp[2], mid = solimp[3], power = solimp[4];
@@ -1440,32 +1455,55 @@ __device__ __forceinline__ float impedance(const float* solimp, float violation)
   float x = fabsf(violation) / width;
   if (x >= 1) return dmax;
   float y;
-  if (power == 1) y = x;
-  else if (power == 2) y = x <= mid ? x * x / mid : 1 - (1 - x) * (1 - x) / (1 - mid);  // MuJoCo's default
+  // (pow2 first and on its own: a specialization keeps no test on the power; the generic
+  // kernel spills more VGPRs with the two power-2 tests merged)
+  if (pow2) y = impedance_pow2(x, mid);
+  else if (power == 1) y = x;
+  else if (power == 2) y = impedance_pow2(x, mid);
   else if (x <= mid) y = powf(x, power) / powf(mid, power - 1);
   else y = 1 - powf(1 - x, power) / powf(1 - mid, power - 1);
   return d0 + y * (dmax - d0);
 }
 
 // row parameters -> D, aref, Rf.  vel = J*qvel.
+// The part that the rows of one constraint share (a pyramid's four edges differ in vel
+// alone): impedance, stiffness, damping, regularizer and its inverse.
+struct RowCoef {
+  float imp, K, B, R, D;
+};
+template <class Ctx>
+__device__ __forceinline__ RowCoef row_coef(const Ctx& c, float pos, float margin, float diag, const float* solref,
+                                            const float* solimp, float rscale) {
+  const DevModel& m = c.mdl();
+  RowCoef k;
+  k.imp = impedance(solimp, pos - margin, c.solimp_pow2 != 0);
+  float tc = fmaxf(solref[0], 2 * m.timestep), dr = solref[1];
+  float dmax = fminf(0.9999f, fmaxf(0.0001f, solimp[1]));
+  k.K = 1.0f / fmaxf(1e-15f, dmax * dmax * tc * tc * dr * dr);
+  k.B = 2.0f / fmaxf(1e-15f, dmax * tc);
+  float R = fmaxf(1e-15f, (1 - k.imp) / k.imp * diag);
+  k.R = fmaxf(1e-15f, R * rscale);
+  k.D = 1.0f / k.R;
+  return k;
+}
+
+// ... and the row's own part: its D (and the friction loss entries), aref from its vel.
+template <class Ctx>
+__device__ __forceinline__ void row_store(const Ctx& c, int r, const RowCoef& k, float pos, float margin, float floss,
+                                          float vel, bool fric) {
+  c.f(c.L.efc_D)[r] = k.D;
+  if (fric) {  // friction rows come first: efc_fl / efc_Rf hold only [0, nfric)
+    c.f(c.L.efc_fl)[r] = floss;
+    c.f(c.L.efc_Rf)[r] = k.R * floss;
+  }
+  float viol = fric ? 0.f : pos - margin;
+  c.f(c.L.efc_aref)[r] = -k.B * vel - k.K * k.imp * viol;
+}
+
 template <class Ctx>
 __device__ __forceinline__ void row_params(const Ctx& c, int r, float pos, float margin, float floss, float diag,
                            const float* solref, const float* solimp, float vel, float rscale, bool fric) {
-  const DevModel& m = c.mdl();
-  float imp = impedance(solimp, pos - margin);
-  float tc = fmaxf(solref[0], 2 * m.timestep), dr = solref[1];
-  float dmax = fminf(0.9999f, fmaxf(0.0001f, solimp[1]));
-  float K = 1.0f / fmaxf(1e-15f, dmax * dmax * tc * tc * dr * dr);
-  float B = 2.0f / fmaxf(1e-15f, dmax * tc);
-  float R = fmaxf(1e-15f, (1 - imp) / imp * diag);
-  R = fmaxf(1e-15f, R * rscale);
-  c.f(c.L.efc_D)[r] = 1.0f / R;
-  if (fric) {  // friction rows come first: efc_fl / efc_Rf hold only [0, nfric)
-    c.f(c.L.efc_fl)[r] = floss;
-    c.f(c.L.efc_Rf)[r] = R * floss;
-  }
-  float viol = fric ? 0.f : pos - margin;
-  c.f(c.L.efc_aref)[r] = -B * vel - K * imp * viol;
+  row_store(c, r, row_coef(c, pos, margin, diag, solref, solimp, rscale), pos, margin, floss, vel, fric);
 }
 
 // sparse contact jacobian (frame rows) -> cj_idx / cj_val; then all rows
@@ -1746,13 +1784,15 @@ __device__ __forceinline__ void make_constraint(const Ctx& c) {
           }
         } else {
           float rs = 2 * cfr0 * cfr0 / m.impratio;
+          // the four edges share every row parameter but vel: computed once
+          const RowCoef rk = row_coef(c, r[12], cmg, ctran, csr, csi, rs);
           for (int e = 0; e < 4; e++) {
             int row = nrow + off + e;
             if (row >= c.L.nefc_max) break;
             int k = 1 + (e >> 1);
             float mu = (k == 1 ? cfr0 : cfr1) * ((e & 1) ? -1.f : 1.f);
             meta[row] = DXR_CON | (e << 4) | (ci << 8);
-            row_params(c, row, r[12], cmg, 0, ctran, csr, csi, cq[3 * ci] + mu * cq[3 * ci + k], rs, false);
+            row_store(c, row, rk, r[12], cmg, 0, cq[3 * ci] + mu * cq[3 * ci + k], false);
           }
         }
       }

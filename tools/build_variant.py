@@ -38,6 +38,9 @@ else:
 if "X(solver)" not in open(os.path.join(src, "dx_device.h")).read():
     B.DIMS = tuple(d for d in B.DIMS if d != "solver")
     B.SOLVER_SPECS = ()
+# ... or from before the impedance's power became one
+if "X(solimp_pow2)" not in open(os.path.join(src, "dx_device.h")).read():
+    B.DIMS = tuple(d for d in B.DIMS if d != "solimp_pow2")
 # csrc includes "../../include/dx.h"
 os.makedirs(os.path.join(ROOT, "variants", "include"), exist_ok=True)
 shutil.copy(os.path.join(ROOT, "include", "dx.h"), os.path.join(ROOT, "variants", "include", "dx.h"))
