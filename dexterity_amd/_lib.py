@@ -17,6 +17,8 @@ LIB_PATH = os.environ.get("DX_LIB") or os.path.join(_HERE, "libdx.so")  # DX_LIB
 QPOS, QVEL, CTRL, QACC_WARMSTART, QACC, TIME = 0, 1, 2, 3, 4, 5
 SITE_XPOS, SITE_VEL, XPOS, XQUAT, NCON, GROUND_CONTACT, NITER, NCAND, STEP_COST = 6, 7, 8, 9, 10, 11, 12, 13, 14
 SENSOR_TORQUE, DIVERGED = 15, 16
+CFRC_EXT, PAD_FORCE = 17, 18  # contact force sensing (dx_contact_enable / dx_contact_set_pads)
+MAX_PADS = 64
 INT_FIELDS = (NCON, GROUND_CONTACT, NITER, NCAND, STEP_COST, DIVERGED)
 HEALTH_WORDS, NCON_HIST = 16, 65
 HEALTH = ("contact_overflow", "candidate_overflow", "jacobian_dof_overflow", "row_overflow", "diverged",
@@ -41,6 +43,8 @@ EXPORTS = (
     "dx_build_key", "dx_env_set_action_filter", "dx_env_action_noise_draw",
     "dx_env_set_hand_observables", "dx_env_hand_obs_dim",
     "dx_env_set_obs_pipeline", "dx_env_obs_pipe_dims", "dx_env_obs_noise_draw",
+    "dx_contact_enable", "dx_contact_set_pads", "dx_contact_npad",
+    "dx_env_set_contact_forces", "dx_env_contact_force_dim", "dx_env_contact_force_bodies",
 )
 COMM_ID_BYTES = 128
 STAGES = ("kinematics", "crb", "broadphase", "midphase", "narrowphase", "constraints", "velocity",
@@ -59,6 +63,7 @@ OUT_HAND_OBS = 9
 # dx_hand_obs.mask, in the order of the row's blocks within a hand
 HOBS_JOINT_POSITIONS, HOBS_TIP_ORIENTATIONS, HOBS_TIP_ANGULAR_VELOCITIES, HOBS_TIP_POSITIONS_EGO = 1, 2, 4, 8
 OUT_OBS_BUFFER = 10
+OUT_CONTACT_FORCE = 11
 # dx_obs_pipeline.padding / .aggregator, by composer's names
 OBS_PAD = {"zero": 0, "initial_value": 1}
 OBS_AGG = {None: 0, "min": 1, "max": 2, "mean": 3, "median": 4, "sum": 5}
@@ -215,6 +220,13 @@ def load(path: str = LIB_PATH):
         L.dx_env_set_obs_pipeline.argtypes = [vp, ctypes.POINTER(ObsPipeline)]
         L.dx_env_obs_pipe_dims.argtypes = [vp, ctypes.POINTER(i32)]
         L.dx_env_obs_noise_draw.argtypes = [vp, i32, vp]
+    if hasattr(L, "dx_contact_enable"):  # (an older variant library for A/B lacks contact force sensing)
+        L.dx_contact_enable.argtypes = [vp, ctypes.c_int]
+        L.dx_contact_set_pads.argtypes = [vp, vp, i32]
+        L.dx_contact_npad.argtypes = [vp]
+        L.dx_env_set_contact_forces.argtypes = [vp, ctypes.c_int]
+        L.dx_env_contact_force_dim.argtypes = [vp]
+        L.dx_env_contact_force_bodies.argtypes = [vp, ctypes.POINTER(i32), i32]
     L.dx_timing_enable.argtypes = [vp, ctypes.c_int]
     L.dx_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i32)]
     L.dx_stage_timing.argtypes = [vp, ctypes.c_int]

@@ -939,6 +939,8 @@ extern "C" int dx_field_width(const dx_model* m, int field) {
     case DX_XPOS: return 3 * d.nbody;
     case DX_XQUAT: return 4 * d.nbody;
     case DX_SENSOR_TORQUE: return 3 * d.nbody;
+    case DX_CFRC_EXT: return 6 * d.nbody;
+    case DX_PAD_FORCE: return 0;  // the pads are a batch's (dx_contact_set_pads): a model has none
   }
   return fail(DX_EINVAL, "unknown field");
 }
@@ -1031,6 +1033,16 @@ struct dx_batch {
   bool debug;
   float* sensor = nullptr;  // DX_SENSOR_TORQUE [nenv][nbody][3] (allocated by dx_sensor_enable)
   float* sen_stash = nullptr;
+  // who reads the stash (DevBatch::sen_stash is set while any does): the torque sensors,
+  // contact sensing (dx_contact_enable), the contact forces of a dx_env
+  enum { STASH_TORQUE = 1, STASH_CONTACT = 2, STASH_ENV = 4 };
+  int stash_users = 0;
+  // contact sensing: DX_CFRC_EXT [nenv][nbody][6], DX_PAD_FORCE [nenv][npad][3] (allocated
+  // for DX_MAX_PADS), the pad table on the device
+  float* cfrc_ext = nullptr;
+  float* pad_force = nullptr;
+  int* pads = nullptr;
+  int npad = 0;
   unsigned* ncon_hist = nullptr;  // dx_ncon_histogram
   // the mid tier beside queued launches (dx_step.hip dx_step_mid_kernel): its stream, the
   // queued workgroups' exit count it waits for (DevBatch::qdone[0])
@@ -1209,6 +1221,8 @@ static void* field_base(dx_batch* b, int field) {
     case DX_STEP_COST: return B.cost;
     case DX_SENSOR_TORQUE: return b->sensor;
     case DX_DIVERGED: return B.bad;
+    case DX_CFRC_EXT: return b->cfrc_ext;
+    case DX_PAD_FORCE: return b->pad_force;
   }
   return nullptr;
 }
@@ -1250,7 +1264,7 @@ extern "C" int dx_get_field(dx_batch* b, int field, void* dst, int32_t env0, int
   if (env0 < 0 || n < 0 || env0 + n > b->nenv) return fail(DX_EINVAL, "bad env range");
   char* base = (char*)field_base(b, field);
   if (!base) return fail(DX_EINVAL, "unknown field");
-  int w = dx_field_width(b->model, field);
+  int w = field == DX_PAD_FORCE ? 3 * b->npad : dx_field_width(b->model, field);
   if (w <= 0) return 0;
   HIPCHK(hipSetDevice(b->device));
   HIPCHK(hipMemcpyAsync(dst, base + (size_t)env0 * w * 4, (size_t)n * w * 4, hipMemcpyDefault, b->stream));
@@ -1315,6 +1329,29 @@ extern "C" int dx_set_watch(dx_batch* b, int32_t geom, int32_t body) {
 static void timing_begin(dx_batch* b, hipEvent_t* start);
 static void timing_end(dx_batch* b, hipEvent_t start);
 
+// The sensor kernel over the batch's stash (dx_sensor.hip): the torque sensors and the
+// batch's contact sensing, whichever are on -- or, with `env_pads`, only a dx_env's pad
+// forces into `env_out`, zero for the envs whose step type is FIRST.
+static int launch_sensor(dx_batch* b, const ContactSense* env_pads, float* env_out) {
+  ContactSense C{};
+  float* torque = nullptr;
+  if (env_pads) {
+    C = *env_pads;
+    C.pad_force = env_out;
+  } else {
+    if (b->stash_users & dx_batch::STASH_TORQUE) torque = b->sensor;
+    if (b->stash_users & dx_batch::STASH_CONTACT) {
+      C.cfrc_ext = b->cfrc_ext;
+      C.pad_force = b->npad ? b->pad_force : nullptr;
+      C.pads = b->pads;
+      C.npad = b->npad;
+    }
+  }
+  HIPCHK(dx_launch_sensor(b->nenv, ((size_t)b->model->lds.total + 6 * DX_MAX_NV) * 4, b->stream, b->dm_dev, b->db,
+                          b->model->lds, torque, C));
+  return 0;
+}
+
 static int launch_step(dx_batch* b, int nsub, int mode) {
   HIPCHK(hipSetDevice(b->device));
   size_t lds = (size_t)b->model->lds.total * 4;
@@ -1370,10 +1407,10 @@ static int launch_step(dx_batch* b, int nsub, int mode) {
     b->qhead_zero = true;
   }
   Bo.mid = 0;
-  // torque sensors from the last substep's stash (mode 0 step, mode 1 forward)
-  if (b->db.sen_stash && mode != 2)
-    HIPCHK(dx_launch_sensor(b->nenv, ((size_t)b->model->lds.total + 6 * DX_MAX_NV) * 4, b->stream, b->dm_dev, b->db,
-                            b->model->lds, b->sensor));
+  // torque sensors and contact sensing from the last substep's stash (mode 0 step, mode 1
+  // forward), one launch for both (a dx_env's contact forces follow its step: env_observe)
+  if ((b->stash_users & (dx_batch::STASH_TORQUE | dx_batch::STASH_CONTACT)) && mode != 2)
+    if (int rc = launch_sensor(b, nullptr, nullptr)) return rc;
   // next launch: heaviest environments first (costs just measured) -- for a model without
   // an overflow tier (contacts disabled), by the order kernel, which also zeroes the queue
   // heads the next queued launch claims from
@@ -1702,21 +1739,70 @@ extern "C" int dx_set_outputs(dx_batch* b, int bodies) {
   return 0;
 }
 
+// The stash's readers: the step kernel writes it while any is on (buffers stay allocated,
+// and their fields readable, until destroy).
+static int stash_use(dx_batch* b, int who, bool on) {
+  if (on && !b->sen_stash) {
+    const size_t E = b->nenv, words = (size_t)b->dm.nq + 2 * b->dm.nv + 1 + 8 * DX_NCON_HI;
+    if (int rc = balloc(b, (void**)&b->sen_stash, E * words * 4)) return rc;
+  }
+  b->stash_users = on ? (b->stash_users | who) : (b->stash_users & ~who);
+  b->db.sen_stash = b->stash_users ? b->sen_stash : nullptr;
+  return 0;
+}
+
 extern "C" int dx_sensor_enable(dx_batch* b, int enable) {
   if (!b) return fail(DX_EINVAL, "null batch");
-  DevBatch& B = b->db;
-  if (enable) {
-    if (!b->sen_stash) {
-      const size_t E = b->nenv, words = (size_t)b->dm.nq + 2 * b->dm.nv + 1 + 8 * DX_NCON_HI;
-      if (int rc = balloc(b, (void**)&b->sen_stash, E * words * 4)) return rc;
-      if (int rc = balloc(b, (void**)&b->sensor, E * 3 * b->dm.nbody * 4)) return rc;
-    }
-    B.sen_stash = b->sen_stash;
-  } else {
-    B.sen_stash = nullptr;  // buffers stay allocated (and the field readable) until destroy
+  if (enable && !b->sensor)
+    if (int rc = balloc(b, (void**)&b->sensor, (size_t)b->nenv * 3 * b->dm.nbody * 4)) return rc;
+  return stash_use(b, dx_batch::STASH_TORQUE, enable != 0);
+}
+
+// ------------------------------------------------------------------------ //
+// contact force sensing (dx_sensor.hip)
+// ------------------------------------------------------------------------ //
+static int contact_alloc(dx_batch* b) {
+  if (b->pads) return 0;
+  const size_t E = b->nenv;
+  if (int rc = balloc(b, (void**)&b->cfrc_ext, E * 6 * b->dm.nbody * 4)) return rc;
+  if (int rc = balloc(b, (void**)&b->pad_force, E * 3 * DX_MAX_PADS * 4)) return rc;
+  return balloc(b, (void**)&b->pads, 2 * DX_MAX_PADS * 4);
+}
+
+extern "C" int dx_contact_enable(dx_batch* b, int enable) {
+  if (!b) return fail(DX_EINVAL, "null batch");
+  HIPCHK(hipSetDevice(b->device));
+  if (enable)
+    if (int rc = contact_alloc(b)) return rc;
+  return stash_use(b, dx_batch::STASH_CONTACT, enable != 0);
+}
+
+static int check_pads(const DevModel& d, const dx_contact_pad* pads, int32_t npad) {
+  if (npad < 0 || (npad > 0 && !pads)) return fail(DX_EINVAL, "contact pads: null table or negative count");
+  if (npad > DX_MAX_PADS) return fail(DX_ELIMIT, "contact pads: more than 64");
+  for (int k = 0; k < npad; k++) {
+    if (pads[k].body < 1 || pads[k].body >= d.nbody) return fail(DX_EINVAL, "contact pads: body outside [1, nbody)");
+    if (pads[k].partner_body < -1 || pads[k].partner_body >= d.nbody)
+      return fail(DX_EINVAL, "contact pads: partner body outside [-1, nbody)");
   }
   return 0;
 }
+
+extern "C" int dx_contact_set_pads(dx_batch* b, const dx_contact_pad* pads, int32_t npad) {
+  if (!b) return fail(DX_EINVAL, "null batch");
+  if (int rc = check_pads(b->dm, pads, npad)) return rc;  // (a rejected call changes nothing)
+  HIPCHK(hipSetDevice(b->device));
+  if (int rc = contact_alloc(b)) return rc;
+  // the stream drained: no launch still reads the old table, and the rows of the new
+  // pads read zero until the next step / forward
+  HIPCHK(hipStreamSynchronize(b->stream));
+  if (npad) HIPCHK(hipMemcpy(b->pads, pads, (size_t)npad * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(b->pad_force, 0, (size_t)b->nenv * 3 * DX_MAX_PADS * 4));
+  b->npad = npad;
+  return 0;
+}
+
+extern "C" int dx_contact_npad(const dx_batch* b) { return b ? b->npad : fail(DX_EINVAL, "null batch"); }
 
 extern "C" int dx_debug_enable(dx_batch* b, int enable) {
   if (!b) return fail(DX_EINVAL, "null batch");
@@ -1824,6 +1910,14 @@ struct dx_env {
   // are sized by the configuration, so they are the env's own (obs_pipe_free), allocated
   // by every accepted call and gone while the pipeline is off
   ObsPipe O{};
+  // the contact forces (dx_env_set_contact_forces): the task's pads -- every hand body with
+  // a collision pair against the prop body, in body order, the prop their partner (empty
+  // for the reach tasks) --, their table on the device and the output (the batch's, from
+  // the first enable on); off while cf_on is false
+  std::vector<dx_contact_pad> cf_pads;
+  ContactSense CF{};
+  float* cf_out = nullptr;
+  bool cf_on = false;
 };
 
 static void obs_pipe_free(ObsPipe& O) {
@@ -1925,6 +2019,20 @@ extern "C" dx_env* dx_env_create_shard(const dx_model* m, int32_t nenv, int32_t 
     return nullptr;
   }
   if (watch_geom >= 0 && dx_set_watch(b, watch_geom, watch_body) != 0) { dx_batch_destroy(b); delete e; return nullptr; }
+  // the contact pads: bodies (other than the world's and the prop's) with a geom pair
+  // against a geom of the prop body, in body order -- the hands' bodies, hand after hand
+  if (task != DX_TASK_REACH && watch_body >= 1 && watch_body < d.nbody) {
+    const auto& gg = m->hi.at("gpair_geom");
+    const auto& gb = m->hi.at("geom_bodyid");
+    std::vector<char> hit(d.nbody, 0);
+    for (int k = 0; k < d.ngpair; k++) {
+      const int b1 = gb[gg[2 * k]], b2 = gb[gg[2 * k + 1]];
+      if (b1 == watch_body && b2 != watch_body) hit[b2] = 1;
+      if (b2 == watch_body && b1 != watch_body) hit[b1] = 1;
+    }
+    for (int k = 1; k < d.nbody; k++)
+      if (hit[k]) e->cf_pads.push_back({k, watch_body});
+  }
   TaskState& S = e->S;
   size_t E = nenv;
   auto al = [&](void** p, size_t bytes) { return balloc(b, p, bytes); };
@@ -2024,6 +2132,11 @@ static int env_hand_obs(dx_env* e) {
 // gather's rows -- all on the batch stream, so the launch point above orders it too.
 // Nothing is launched while the pipeline is off.
 static int env_observe(dx_env* e) {
+  // the contact forces (dx_sensor.hip) of the step's last physics step, zero for the envs
+  // that returned FIRST: at the same launch point, where every tier has written its stash
+  // and the step types
+  if (e->cf_on)
+    if (int rc = launch_sensor(e->batch, &e->CF, e->cf_out)) return rc;
   if (int rc = env_hand_obs(e)) return rc;
   if (!e->O.on) return 0;
   HIPCHK(dx_launch_obs_pipe(e->batch->stream, e->O, 0));
@@ -2326,6 +2439,56 @@ extern "C" int dx_env_hand_obs_dim(const dx_env* e) {
 }
 
 // ------------------------------------------------------------------------ //
+// the contact forces of the task's pads (dx_sensor.hip, launched by env_observe)
+// ------------------------------------------------------------------------ //
+extern "C" int dx_env_set_contact_forces(dx_env* e, int enable) {
+  if (!e) return fail(DX_EINVAL, "null env");
+  dx_batch* b = e->batch;
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));  // may be called between steps
+  if (!enable) {  // off: a control step launches what an env never configured launches
+    e->cf_on = false;
+    return stash_use(b, dx_batch::STASH_ENV, false);
+  }
+  // (a reach scene's pairs have a margin: a collision-free reset state can carry force,
+  // and a reset env runs no forward pass that would solve it)
+  if (e->P.kind == DX_KIND_REACH) return fail(DX_EINVAL, "contact forces: the reach tasks have no prop to touch");
+  const int npad = (int)e->cf_pads.size();
+  if (npad < 1) return fail(DX_EINVAL, "contact forces: no body has a collision pair with the prop");
+  if (npad > DX_MAX_PADS) return fail(DX_ELIMIT, "contact forces: more than 64 pads");
+  const size_t bytes = (size_t)e->P.nenv * 3 * npad * 4;
+  if (!e->cf_out) {
+    float* out = nullptr;
+    int* pads = nullptr;
+    if (int rc = balloc(b, (void**)&out, bytes)) return rc;
+    if (int rc = balloc(b, (void**)&pads, (size_t)npad * 8)) return rc;
+    HIPCHK(hipStreamSynchronize(b->stream));  // balloc zeroes on the stream: ahead of the copy
+    HIPCHK(hipMemcpy(pads, e->cf_pads.data(), (size_t)npad * 8, hipMemcpyHostToDevice));
+    e->cf_out = out;
+    e->CF.pads = pads;
+    e->CF.npad = npad;
+    e->CF.first = e->S.step_type;
+  }
+  if (int rc = stash_use(b, dx_batch::STASH_ENV, true)) return rc;
+  // zeros until the next step: the stash holds nothing of the current episode
+  if (!e->cf_on) HIPCHK(hipMemset(e->cf_out, 0, bytes));
+  e->cf_on = true;
+  return 0;
+}
+
+extern "C" int dx_env_contact_force_dim(const dx_env* e) {
+  if (!e) return fail(DX_EINVAL, "null env");
+  return e->cf_on ? 3 * (int)e->cf_pads.size() : 0;
+}
+
+extern "C" int dx_env_contact_force_bodies(const dx_env* e, int32_t* out, int32_t n) {
+  if (!e || (n > 0 && !out)) return fail(DX_EINVAL, "null argument");
+  if (e->P.kind == DX_KIND_REACH) return fail(DX_EINVAL, "contact forces: the reach tasks have no prop to touch");
+  for (int k = 0; k < n && k < (int)e->cf_pads.size(); k++) out[k] = e->cf_pads[k].body;
+  return (int)e->cf_pads.size();
+}
+
+// ------------------------------------------------------------------------ //
 // the observation pipeline (dx_obspipe.hip dx_obs_pipe_kernel)
 // ------------------------------------------------------------------------ //
 extern "C" int dx_env_set_obs_pipeline(dx_env* e, const dx_obs_pipeline* p) {
@@ -2511,6 +2674,8 @@ static std::vector<StateField> env_state_fields(dx_env* e) {
     if (O.noise) f.push_back({"mt_obs_noise", O.mt, E * DX_MTW_WORDS * 4});
     f.push_back({"obs_buffer", O.out, E * (O.agg ? 1 : O.K) * O.W * 4});
   }
+  // the contact forces' rows, while they are on (as the hand observables' rows above)
+  if (e->cf_on) f.push_back({"contact_force", e->cf_out, E * 3 * e->cf_pads.size() * 4});
   return f;
 }
 
@@ -2587,6 +2752,10 @@ extern "C" int dx_env_output(dx_env* e, int which, void** devptr) {
     case DX_OUT_OBS_BUFFER:
       if (!e->O.on) return fail(DX_EINVAL, "no observation buffer: the observation pipeline is off (dx_env_set_obs_pipeline)");
       *devptr = e->O.out;
+      return 0;
+    case DX_OUT_CONTACT_FORCE:
+      if (!e->cf_on) return fail(DX_EINVAL, "no contact forces: dx_env_set_contact_forces has not enabled them");
+      *devptr = e->cf_out;
       return 0;
   }
   return fail(DX_EINVAL, "unknown output");

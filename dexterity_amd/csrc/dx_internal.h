@@ -477,9 +477,19 @@ hipError_t dx_launch_step_hi(int grid, size_t lds, hipStream_t stream, const Dev
 hipError_t dx_launch_step_mid(int grid, size_t lds, hipStream_t stream, const DevModel* mdev, const DevBatch& B,
                               const Lds& L, int nsub, unsigned target);
 
-// dx_sensor.hip: joint torque sensors from the step kernel's stash (host side)
+// dx_sensor.hip: joint torque sensors and contact force sensing from the step kernel's
+// stash (host side).  Every output is optional: `out` (the torque sensors) and the two of
+// ContactSense are written only when set.
+#define DX_MAX_PADS 64       // lane = pad
+struct ContactSense {
+  float* cfrc_ext;           // DX_CFRC_EXT [nenv][nbody][6] (torque, force), or null
+  float* pad_force;          // DX_PAD_FORCE [nenv][npad][3], or null
+  const int* pads;           // [npad][2]: body, partner body (-1: any)
+  int npad;
+  const int* first;          // step types [nenv], or null: an env at 0 (FIRST) gets zero rows
+};
 hipError_t dx_launch_sensor(int nenv, size_t lds, hipStream_t stream, const DevModel* mdev, const DevBatch& B,
-                            const Lds& L, float* out);
+                            const Lds& L, float* out, const ContactSense& C);
 
 // dx_ik.hip: site Jacobians and batched damped-least-squares IK (host side).
 struct IkDev {

@@ -14,6 +14,17 @@
 // kernel rebuilds the tree quantities from the stash, one 64-lane wave per env,
 // lane = body (nbody <= 64), and writes the sensor of every body:
 //   DX_SENSOR_TORQUE [nenv][nbody][3]  (site at the body origin, body frame).
+//
+// Contact force sensing (include/dx.h dx_contact_enable) reads the same stash in the same
+// launch: the kinematics at the stashed qpos, then the stashed contacts in list order (so
+// the sums are deterministic), lane = output:
+//   DX_CFRC_EXT  [nenv][nbody][6]  MuJoCo's cfrc_ext ([3P] mj_rnePostConstraint): torque about
+//     the subtree com of the body's tree root, then force, world axes -- xfrc_applied moved
+//     from xipos, plus every contact's force (+ on body 2, - on body 1); lane = body.
+//   DX_PAD_FORCE [nenv][npad][3]   the force the contacts with a pad's partner body (-1: any
+//     body) exert on the pad's body, in that body's frame (xmat^T F); lane = pad.
+// Each output is written only when its pointer is set; the torque sensors' arithmetic does
+// not depend on which of the others are on.
 #include "dx_device.h"
 
 // Stash layout per env (floats): qpos [nq] | qvel [nv] | qacc [nv] | ncon (int bits) |
@@ -21,11 +32,21 @@
 __host__ __device__ inline int dx_sensor_stash_words(int nq, int nv) { return nq + 2 * nv + 1 + 8 * DX_NCON_HI; }
 
 extern "C" __global__ void __launch_bounds__(64) dx_sensor_kernel(const DevModel* __restrict__ mp, DevBatch B, Lds L,
-                                                                  float* out) {
+                                                                  float* out, ContactSense C) {
   extern __shared__ float smem[];
   const DevModel& m = *(const DevModel*)(const DXG DevModel*)mp;
   const int env = (int)blockIdx.x;
   if (env >= B.nenv) return;
+  // an env whose step returned FIRST (dx_env_step) ran no physics step: its stash is stale,
+  // and the forces of a freshly reset env are zero
+  const bool stale = C.first && C.first[env] == 0;
+  if (stale) {
+    if (C.cfrc_ext)
+      for (int k = LANE; k < 6 * m.nbody; k += DX_WAVE) C.cfrc_ext[(size_t)env * 6 * m.nbody + k] = 0.f;
+    if (C.pad_force)
+      for (int k = LANE; k < 3 * C.npad; k += DX_WAVE) C.pad_force[(size_t)env * 3 * C.npad + k] = 0.f;
+    if (!out) return;
+  }
   CtxT<SpecRT> c(m, L, smem, nullptr, nullptr);
   c.I = (int*)(smem + L.ints);
   for (int k = LANE; k < L.total + 6 * DX_MAX_NV; k += DX_WAVE) smem[k] = 0.f;
@@ -49,6 +70,54 @@ extern "C" __global__ void __launch_bounds__(64) dx_sensor_kernel(const DevModel
   const float* xmat = c.f(L.xmat);
   const float* xipos = c.f(L.xipos);
   const float* rcom = c.f(L.rcom);
+  const int ncon = min(__float_as_int(st[nq + 2 * nv]), DX_NCON_HI);
+  const float* cs = st + nq + 2 * nv + 1;
+  const int b = LANE;
+  if (C.cfrc_ext && !stale && b < nb) {  // lane = body
+    float f[6] = {0, 0, 0, 0, 0, 0};
+    if (b >= 1) {
+      const float* rc = rcom + 3 * m.body_rootidx[b];
+      if (B.xfrc) {  // applied wrench at the body com (xfrc rows: force, torque)
+        const float* x6 = B.xfrc + 6 * b;
+        const float off[3] = {xipos[3 * b] - rc[0], xipos[3 * b + 1] - rc[1], xipos[3 * b + 2] - rc[2]};
+        float tq[3];
+        cross3(tq, off, x6);
+        f[0] = x6[3] + tq[0]; f[1] = x6[4] + tq[1]; f[2] = x6[5] + tq[2];
+        f[3] = x6[0]; f[4] = x6[1]; f[5] = x6[2];
+      }
+      for (int ci = 0; ci < ncon; ci++) {  // contact force: on b2, its reaction on b1
+        const float* r = cs + 8 * ci;
+        const int b1 = __float_as_int(r[0]), b2 = __float_as_int(r[1]);
+        if (b != b1 && b != b2) continue;
+        const float s = b == b2 ? 1.f : -1.f;
+        const float off[3] = {r[2] - rc[0], r[3] - rc[1], r[4] - rc[2]};
+        float tq[3];
+        cross3(tq, off, r + 5);
+        f[0] += s * tq[0]; f[1] += s * tq[1]; f[2] += s * tq[2];
+        f[3] += s * r[5]; f[4] += s * r[6]; f[5] += s * r[7];
+      }
+    }
+    float* o = C.cfrc_ext + ((size_t)env * nb + b) * 6;
+    for (int x = 0; x < 6; x++) o[x] = f[x];
+  }
+  if (C.pad_force && !stale && LANE < C.npad) {  // lane = pad
+    const int body = C.pads[2 * LANE], partner = C.pads[2 * LANE + 1];
+    float F[3] = {0, 0, 0};
+    for (int ci = 0; ci < ncon; ci++) {
+      const float* r = cs + 8 * ci;
+      const int b1 = __float_as_int(r[0]), b2 = __float_as_int(r[1]);
+      const bool on2 = b2 == body && (partner < 0 || b1 == partner);
+      const bool on1 = b1 == body && (partner < 0 || b2 == partner);
+      if (!on1 && !on2) continue;
+      const float s = on2 ? 1.f : -1.f;
+      F[0] += s * r[5]; F[1] += s * r[6]; F[2] += s * r[7];
+    }
+    float v[3];
+    mattvec3(v, xmat + 9 * body, F);
+    float* o = C.pad_force + ((size_t)env * C.npad + LANE) * 3;
+    o[0] = v[0]; o[1] = v[1]; o[2] = v[2];
+  }
+  if (!out) return;  // (uniform: no torque sensors in this launch)
   // cdof_dot, lane = dof (mj_comVel as chain sums, as dx_step.hip velocity_stage)
   for (int d = LANE; d < nv; d += DX_WAVE) {
     const float4 d0 = m.dof_rec[2 * d], d1 = m.dof_rec[2 * d + 1];
@@ -68,9 +137,6 @@ extern "C" __global__ void __launch_bounds__(64) dx_sensor_kernel(const DevModel
   SYNC();
   // lane = body: cfrc_body - cfrc_ext, com frame of the body's tree
   float* acc = smem + L.total;  // [nbody][6]
-  const int ncon = __float_as_int(st[nq + 2 * nv]);
-  const float* cs = st + nq + 2 * nv + 1;
-  const int b = LANE;
   if (b >= 1 && b < nb) {
     const uint64_t ch = m.body_chain[b];
     const float* rc = rcom + 3 * m.body_rootidx[b];
@@ -136,7 +202,7 @@ extern "C" __global__ void __launch_bounds__(64) dx_sensor_kernel(const DevModel
 }
 
 hipError_t dx_launch_sensor(int nenv, size_t lds, hipStream_t stream, const DevModel* mdev, const DevBatch& B,
-                            const Lds& L, float* out) {
-  hipLaunchKernelGGL(dx_sensor_kernel, dim3(nenv), dim3(64), lds, stream, mdev, B, L, out);
+                            const Lds& L, float* out, const ContactSense& C) {
+  hipLaunchKernelGGL(dx_sensor_kernel, dim3(nenv), dim3(64), lds, stream, mdev, B, L, out, C);
   return hipGetLastError();
 }

@@ -75,6 +75,7 @@ HAND_EXTRA_OBSERVABLES = collections.OrderedDict((
     ("fingertip_positions_ego", (_lib.HOBS_TIP_POSITIONS_EGO, 0, 3)),
 ))
 HAND_ROOT_BODY = "forearm"  # hand.root_body: shadow_hand_e.py:62, adroit_hand.py:57
+CONTACT_FORCES_KEY = "hand_contact_forces"  # GoalEnvironment.enable_contact_forces
 
 
 def _whole_number(name: str, value) -> int:
@@ -504,6 +505,8 @@ class GoalEnvironment:
         # configure_observations' current settings (None: the observation pipeline is off)
         self.observation_config = None
         self._obs_pipe = None  # (row width W, delivered rows per env, aggregated)
+        # enable_contact_forces: the pads of DX_OUT_CONTACT_FORCE (0: off)
+        self.contact_force_pads = 0
         if np.isfinite(self.time_limit):
             _lib.check(L.dx_env_set_time_limit(self.ptr, self.time_limit))
         # max_time_per_goal in fp64 (the params carry it as a float)
@@ -541,10 +544,14 @@ class GoalEnvironment:
         if self._obs_pipe is not None:  # composer: (buffer_size, n), no buffer axis behind an aggregator
             _, rows, aggregated = self._obs_pipe
             lead = () if aggregated or (rows == 1 and self.strip_singleton_obs_buffer_dim) else (rows,)
-        return collections.OrderedDict(
+        spec = collections.OrderedDict(
             (k, Array(lead + (s.stop - s.start,), np.float64, name=k))
             for k, s in list(self._layout.items()) + list(self._hand_layout.items())
         )
+        if self.contact_force_pads:  # (never buffered: the observation pipeline's row does not carry them)
+            lead = () if self.strip_singleton_obs_buffer_dim else (1,)
+            spec[CONTACT_FORCES_KEY] = Array(lead + (self.contact_force_pads, 3), np.float64, name=CONTACT_FORCES_KEY)
+        return spec
 
     # ---------------------------------------------------------------- stepping
     def reset(self) -> TimeStep:
@@ -559,6 +566,15 @@ class GoalEnvironment:
             rows = self.hand_obs()
             for k, s in self._hand_layout.items():
                 out[k] = (rows[:, s] if self.strip_singleton_obs_buffer_dim else rows[:, None, s]).astype(np.float64)
+        return out
+
+    def _contact_observation(self) -> "collections.OrderedDict[str, np.ndarray]":
+        """`hand_contact_forces` while enable_contact_forces is on (one device-to-host copy of
+        DX_OUT_CONTACT_FORCE); empty, and no copy, while it is off."""
+        out = collections.OrderedDict()
+        if self.contact_force_pads:
+            rows = self.contact_forces().astype(np.float64)
+            out[CONTACT_FORCES_KEY] = rows if self.strip_singleton_obs_buffer_dim else rows[:, None]
         return out
 
     def step(self, action, device_action: bool = False) -> Optional[TimeStep]:
@@ -581,9 +597,10 @@ class GoalEnvironment:
         _lib.check(L.dx_env_step_host(self.ptr, self._pin_act.ctypes.data, self._pin_out.ctypes.data))
         ts = self._timestep_packed(self._pin_out)
         if self._obs_pipe is not None:  # the packed row keeps the raw observation: one more copy
-            return ts._replace(observation=self._pipeline_observation())
-        if self.hand_obs_dim:  # the packed row does not carry them: one more copy
+            ts = ts._replace(observation=self._pipeline_observation())
+        elif self.hand_obs_dim:  # the packed row does not carry them: one more copy
             ts.observation.update(self._hand_observation())
+        ts.observation.update(self._contact_observation())
         return ts
 
     def _timestep_packed(self, packed: np.ndarray) -> TimeStep:
@@ -689,6 +706,47 @@ class GoalEnvironment:
     def hand_obs(self) -> np.ndarray:
         """[num_envs, hand_obs_dim] float32 host copy of the rows (DxError while off)."""
         return self._read(_lib.OUT_HAND_OBS, np.float32, self.hand_obs_dim)
+
+    # ---------------------------------------------------------------- contact forces
+    def enable_contact_forces(self, enable: bool = True) -> None:
+        """Tactile force between the hands and the prop, on the device behind every control
+        step (include/dx.h dx_env_set_contact_forces): for every hand body that can collide
+        with the prop (`contact_force_bodies`; 23 per Shadow hand) the force the prop's
+        contacts exert on it, in that body's frame.  It arrives as `hand_contact_forces`,
+        [B, npad, 3], after the other keys of `observation_spec()` and of every TimeStep: the
+        last physics step's forces on MID and LAST steps, zeros on FIRST ones and until the
+        first step after enabling.  A checkpoint carries the rows but not this setting.  The
+        reach tasks have no prop: ValueError."""
+        if self.task.kind == _lib.TASK_REACH:
+            raise ValueError("contact forces need a prop: the reach tasks have none")
+        L = _lib.load()
+        _lib.check(L.dx_env_set_contact_forces(self.ptr, int(bool(enable))))
+        dim = _lib.check(L.dx_env_contact_force_dim(self.ptr))
+        assert dim % 3 == 0 and (dim > 0) == bool(enable), dim
+        self.contact_force_pads = dim // 3
+
+    @property
+    def contact_force_bodies(self):
+        """Names of the pads' bodies, in the order of the rows of `contact_forces()`."""
+        if self.task.kind == _lib.TASK_REACH:
+            raise ValueError("contact forces need a prop: the reach tasks have none")
+        L = _lib.load()
+        ids = (ctypes.c_int32 * _lib.MAX_PADS)()
+        n = _lib.check(L.dx_env_contact_force_bodies(self.ptr, ids, _lib.MAX_PADS))
+        names = self.task.compiled.names["body"]
+        return [names[i] for i in list(ids)[:n]]
+
+    @property
+    def contact_force_ptr(self) -> int:
+        """Device address of the [num_envs, npad, 3] float32 forces (while enabled)."""
+        return self._out(_lib.OUT_CONTACT_FORCE)
+
+    def contact_forces(self) -> np.ndarray:
+        """[num_envs, npad, 3] float32 host copy of DX_OUT_CONTACT_FORCE (DxError while off)."""
+        if not self.contact_force_pads:
+            raise _lib.DxError("contact forces are off (enable_contact_forces)")
+        n = self.contact_force_pads
+        return self._read(_lib.OUT_CONTACT_FORCE, np.float32, 3 * n).reshape(self.num_envs, n, 3)
 
     # ---------------------------------------------------------------- observation pipeline
     def _row_layout(self) -> "collections.OrderedDict[str, slice]":
@@ -824,6 +882,9 @@ class GoalEnvironment:
                 if (key in z.files) != (key in {name for name, _, _ in fields}):
                     raise ValueError("checkpoint and env differ in the observation pipeline (on in one, off in the "
                                      "other, or its noise): configure_observations as the saved env did, then load")
+            if ("contact_force" in z.files) != ("contact_force" in {name for name, _, _ in fields}):
+                raise ValueError("checkpoint and env differ in the contact forces (on in one, off in the other): "
+                                 "enable_contact_forces as the saved env did, then load")
             nbytes = sum(nb for _, _, nb in fields)
             buf = np.empty(nbytes, dtype=np.uint8)
             for name, off, nb in fields:
@@ -856,6 +917,7 @@ class GoalEnvironment:
             observation = self._pipeline_observation()
         else:
             observation.update(self._hand_observation())
+        observation.update(self._contact_observation())
         return TimeStep(st.astype(np.int32), rew, disc, observation)
 
     def goals(self) -> np.ndarray:

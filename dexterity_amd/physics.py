@@ -164,6 +164,34 @@ class BatchedPhysics:
         bodies = np.asarray(joints, dtype=int)
         return np.einsum("ejk,jk->ej", s[:, bodies, :], np.asarray(axes, dtype=np.float64))
 
+    def enable_contact_forces(self, enable: bool = True) -> None:
+        """Contact force sensing (include/dx.h dx_contact_enable): every step / forward then
+        also writes DX_CFRC_EXT and, for the pads of `set_contact_pads`, DX_PAD_FORCE."""
+        _lib.check(_lib.load().dx_contact_enable(self.ptr, int(enable)))
+
+    def set_contact_pads(self, bodies, partners=-1) -> None:
+        """The pads of DX_PAD_FORCE: pad k reports the force that contacts with body
+        `partners[k]` (-1: any body; one value serves every pad) exert on `bodies[k]`, in
+        that body's frame.  An empty list clears them; at most 64."""
+        b = np.asarray(bodies, dtype=np.int32).reshape(-1)
+        pads = np.empty((len(b), 2), dtype=np.int32)
+        pads[:, 0] = b
+        pads[:, 1] = np.broadcast_to(np.asarray(partners, dtype=np.int32), b.shape)
+        _lib.check(_lib.load().dx_contact_set_pads(self.ptr, pads.ctypes.data if len(b) else None, len(b)))
+
+    def cfrc_ext(self) -> np.ndarray:
+        """MuJoCo's `cfrc_ext` of every env, [B, nbody, 6]: per body the torque about the
+        subtree com of its tree root, then the force, world axes (DX_CFRC_EXT)."""
+        return self.get(_lib.CFRC_EXT).reshape(self.nenv, -1, 6)
+
+    def pad_forces(self) -> np.ndarray:
+        """[B, npad, 3]: each pad's contact force in its body's frame (DX_PAD_FORCE)."""
+        npad = _lib.check(_lib.load().dx_contact_npad(self.ptr))
+        out = np.zeros((self.nenv, npad, 3), dtype=np.float32)
+        if npad:
+            _lib.check(_lib.load().dx_get_field(self.ptr, _lib.PAD_FORCE, out.ctypes.data, 0, self.nenv))
+        return out
+
     def debug(self, enable: bool = True) -> None:
         _lib.check(_lib.load().dx_debug_enable(self.ptr, int(enable)))
 

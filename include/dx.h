@@ -80,6 +80,13 @@ enum dx_field {
   DX_DIVERGED = 16,     /* 1  (int32 bits) r: the env's state diverged during the last dx_step /
                            dx_forward (a non-finite qpos / qvel / qacc, or |qacc| > 1e10: MuJoCo's
                            BADQACC, [3P] mj_checkAcc) and was reset to qpos0 (mj_resetData) */
+  DX_CFRC_EXT = 17,     /* 6*nbody  r  (after dx_contact_enable): MuJoCo's cfrc_ext, per body
+                           [torque(3) about the subtree com of the body's tree root, force(3)],
+                           world axes; the world body's row is zero */
+  DX_PAD_FORCE = 18,    /* 3*npad   r  (after dx_contact_enable, pads from dx_contact_set_pads):
+                           per pad the contact force on its body, in the body's frame.  The pads
+                           are a batch's: dx_field_width (a model's) answers 0, a batch's width is
+                           3 * dx_contact_npad */
   DX_NFIELD
 };
 
@@ -145,6 +152,29 @@ int dx_set_outputs(dx_batch* b, int bodies);
 /* Enables DX_SENSOR_TORQUE: dx_step / dx_forward then also compute every body's torque
  * sensor (one extra small kernel per call; nothing when disabled). */
 int dx_sensor_enable(dx_batch* b, int enable);
+
+/* Contact force sensing -------------------------------------------------- */
+/* The contact forces the step solves, read back from the same stash and in the same small
+ * kernel as the torque sensors (one launch for both when both are on; nothing when all is
+ * off), with their timing: after dx_step(n) they describe the last physics step before its
+ * integration (mj_sensorAcc in mj_step2, as after dm_control's physics.step()), after
+ * dx_forward the current state.  Contacts up to DX_NCON_HI, whichever tier ran the step; the
+ * sums run in the contact list's order, so results are deterministic.
+ *  DX_CFRC_EXT   [3P] mj_rnePostConstraint's cfrc_ext: xfrc_applied moved from xipos, plus
+ *    every contact's force (+ on its body 2, - on its body 1), layout and content as
+ *    d->cfrc_ext.
+ *  DX_PAD_FORCE  for each configured pad {body, partner_body}: the sum of the forces that
+ *    contacts with partner_body (-1: any body, the world body's geoms included) exert on
+ *    body, in body's frame at that state (xmat^T F).  No torque and no count; a MuJoCo
+ *    `touch` scalar needs the contact normal, which the stash does not carry.
+ * dx_contact_set_pads: npad = 0 clears the pads; DX_EINVAL when a body is outside [1, nbody)
+ * or a partner outside [-1, nbody), DX_ELIMIT above 64 pads; a rejected call leaves the
+ * configuration unchanged.  It synchronises the stream, and the rows read zero until the
+ * next dx_step / dx_forward. */
+int dx_contact_enable(dx_batch* b, int enable);
+typedef struct { int32_t body, partner_body; } dx_contact_pad;
+int dx_contact_set_pads(dx_batch* b, const dx_contact_pad* pads, int32_t npad);
+int dx_contact_npad(const dx_batch* b);
 
 /* Health (always on) ----------------------------------------------------- */
 /* Counters of capacity overflows and divergences since the batch was created or last
@@ -241,7 +271,9 @@ enum dx_env_out { DX_OUT_OBS = 0, DX_OUT_REWARD = 1, DX_OUT_DISCOUNT = 2, DX_OUT
                                          observables; while they are on (below) */,
                   DX_OUT_OBS_BUFFER = 10 /* [nenv][K][W] f32 oldest first, or [nenv][W] with an
                                             aggregator: the observation pipeline's delivered rows;
-                                            while it is on (below) */ };
+                                            while it is on (below) */,
+                  DX_OUT_CONTACT_FORCE = 11 /* [nenv][3 * npad] f32, the contact forces of the task's
+                                               pads; while they are on (below) */ };
 dx_env* dx_env_create(const dx_model* m, int32_t nenv, int32_t device, int32_t task, uint64_t seed,
                       const float* params, int32_t nparams);
 /* One shard of a job's environments: this handle's env e is the job's env env0 + e.
@@ -369,6 +401,29 @@ typedef struct dx_hand_obs {
 int dx_env_set_hand_observables(dx_env* e, const dx_hand_obs* cfg);
 /* Row width of DX_OUT_HAND_OBS; 0 while the feature is off. */
 int dx_env_hand_obs_dim(const dx_env* e);
+
+/* The contact forces between the hands and the prop (DX_PAD_FORCE at the env level): the
+ * pads are fixed by the task -- per hand, in body order, every hand body that has a
+ * collision pair with a geom of the task's prop body (params word 23), the prop their
+ * partner: 23 for the Shadow reorient scene, 2 x 23 for the handover.  DX_OUT_CONTACT_FORCE is
+ * a library-owned [nenv][3 * npad] f32 buffer, each pad's force in its body's frame, written
+ * by one small kernel behind every control step (and dx_env_reset).
+ *  - MID and LAST rows are those of the step's last physics step (the torque sensors' timing).
+ *  - Rows are zero after dx_env_reset and for every env whose step returned FIRST: such an
+ *    env ran no physics step, and a freshly spawned prop touches nothing.
+ *  - Enabling between steps is allowed (it synchronises the stream) and leaves zeros until
+ *    the next step.
+ * Off is the default: the launches, every output and the checkpoint are then those of an env
+ * never configured, and dx_env_output(DX_OUT_CONTACT_FORCE) fails.  While on, the checkpoint
+ * carries the buffer as its last field, contact_force, but not the setting.  DX_OUT_OBS, the
+ * packed rows, dx_env_step_host, the all-gather and the observation pipeline's row are
+ * unaffected.  The reach tasks return DX_EINVAL: they have no prop, and Adroit's pairs have a
+ * margin, so a collision-free reset state can carry force that no forward pass solves.
+ * dx_env_contact_force_dim: 3 * npad while on, else 0.  dx_env_contact_force_bodies: the pads'
+ * body ids into out[0 .. min(n, npad)), returns npad (on or off). */
+int dx_env_set_contact_forces(dx_env* e, int enable);
+int dx_env_contact_force_dim(const dx_env* e);
+int dx_env_contact_force_bodies(const dx_env* e, int32_t* out, int32_t n);
 
 /* The observation pipeline: the options the reference gives every observable
  * (ObservableSpec, manipulation/shared/observations.py:8-17, handed on by make_options
