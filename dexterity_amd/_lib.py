@@ -45,6 +45,7 @@ EXPORTS = (
     "dx_env_set_obs_pipeline", "dx_env_obs_pipe_dims", "dx_env_obs_noise_draw",
     "dx_contact_enable", "dx_contact_set_pads", "dx_contact_npad",
     "dx_env_set_contact_forces", "dx_env_contact_force_dim", "dx_env_contact_force_bodies",
+    "dx_set_xfrc_env", "dx_get_xfrc_env", "dx_xfrc_ptr", "dx_env_set_perturbation", "dx_env_perturb_draw",
 )
 COMM_ID_BYTES = 128
 STAGES = ("kinematics", "crb", "broadphase", "midphase", "narrowphase", "constraints", "velocity",
@@ -64,6 +65,8 @@ OUT_HAND_OBS = 9
 HOBS_JOINT_POSITIONS, HOBS_TIP_ORIENTATIONS, HOBS_TIP_ANGULAR_VELOCITIES, HOBS_TIP_POSITIONS_EGO = 1, 2, 4, 8
 OUT_OBS_BUFFER = 10
 OUT_CONTACT_FORCE = 11
+OUT_PERTURB = 12
+PERTURB_MAX_BODIES = 4
 # dx_obs_pipeline.padding / .aggregator, by composer's names
 OBS_PAD = {"zero": 0, "initial_value": 1}
 OBS_AGG = {None: 0, "min": 1, "max": 2, "mean": 3, "median": 4, "sum": 5}
@@ -129,6 +132,22 @@ class ObsPipeline(ctypes.Structure):
         ("noise_seed", ctypes.c_uint64),
         ("noise_sigma", ctypes.c_void_p),
         ("nsigma", ctypes.c_int32),
+    ]
+
+
+class Perturbation(ctypes.Structure):
+    """struct dx_perturbation (include/dx.h)."""
+
+    _fields_ = [
+        ("nbody", ctypes.c_int32),
+        ("bodies", ctypes.c_int32 * 4),
+        ("probability", ctypes.c_double),
+        ("force_min", ctypes.c_double),
+        ("force_max", ctypes.c_double),
+        ("torque_min", ctypes.c_double),
+        ("torque_max", ctypes.c_double),
+        ("duration", ctypes.c_int32),
+        ("seed", ctypes.c_uint64),
     ]
 
 
@@ -227,6 +246,12 @@ def load(path: str = LIB_PATH):
         L.dx_env_set_contact_forces.argtypes = [vp, ctypes.c_int]
         L.dx_env_contact_force_dim.argtypes = [vp]
         L.dx_env_contact_force_bodies.argtypes = [vp, ctypes.POINTER(i32), i32]
+    if hasattr(L, "dx_set_xfrc_env"):  # (an older variant library for A/B lacks per-env wrenches and the pushes)
+        L.dx_set_xfrc_env.argtypes = [vp, vp, i32, i32]
+        L.dx_get_xfrc_env.argtypes = [vp, vp, i32, i32]
+        L.dx_xfrc_ptr.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(i32)]
+        L.dx_env_set_perturbation.argtypes = [vp, ctypes.POINTER(Perturbation)]
+        L.dx_env_perturb_draw.argtypes = [vp, i32, vp]
     L.dx_timing_enable.argtypes = [vp, ctypes.c_int]
     L.dx_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i32)]
     L.dx_stage_timing.argtypes = [vp, ctypes.c_int]

@@ -1029,6 +1029,7 @@ struct dx_batch {
   int slots;   // persistent workgroups of a queued launch
   int hi_grid; // workgroups of the overflow tier's launch
   float* xfrc;
+  float* xfrc_env = nullptr;  // [nenv][nbody][6], allocated by the first dx_set_xfrc_env
   std::vector<void*> allocs;
   bool debug;
   float* sensor = nullptr;  // DX_SENSOR_TORQUE [nenv][nbody][3] (allocated by dx_sensor_enable)
@@ -1274,11 +1275,66 @@ extern "C" int dx_get_field(dx_batch* b, int field, void* dst, int32_t env0, int
 
 extern "C" int dx_set_xfrc(dx_batch* b, const float* xfrc, int32_t nbody) {
   if (!b) return fail(DX_EINVAL, "null batch");
-  if (!xfrc) { b->db.xfrc = nullptr; return 0; }
+  if (!xfrc) {  // (the unused shared array is kept zero: what every env then reads back)
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipMemsetAsync(b->xfrc, 0, (size_t)b->dm.nbody * 6 * 4, b->stream));
+    b->db.xfrc = nullptr;
+    b->db.xfrc_stride = 0;
+    return 0;
+  }
   if (nbody != b->dm.nbody) return fail(DX_EINVAL, "xfrc must be [nbody][6]");
   HIPCHK(hipSetDevice(b->device));
   HIPCHK(hipMemcpyAsync(b->xfrc, xfrc, (size_t)nbody * 6 * 4, hipMemcpyDefault, b->stream));
   b->db.xfrc = b->xfrc;
+  b->db.xfrc_stride = 0;
+  return 0;
+}
+
+// Shared -> per-env mode: every env's rows start as the shared array (zero without one,
+// dx_set_xfrc), by doubling copies on the stream.
+static int xfrc_env_mode(dx_batch* b) {
+  if (b->db.xfrc_stride) return 0;
+  const size_t row = (size_t)b->dm.nbody * 6 * 4;
+  HIPCHK(hipSetDevice(b->device));
+  if (!b->xfrc_env && balloc(b, (void**)&b->xfrc_env, (size_t)b->nenv * row)) return DX_EHIP;
+  HIPCHK(hipMemcpyAsync(b->xfrc_env, b->xfrc, row, hipMemcpyDeviceToDevice, b->stream));
+  for (size_t have = 1; have < (size_t)b->nenv; have *= 2) {
+    const size_t n = std::min(have, (size_t)b->nenv - have);
+    HIPCHK(hipMemcpyAsync((char*)b->xfrc_env + have * row, b->xfrc_env, n * row, hipMemcpyDeviceToDevice, b->stream));
+  }
+  b->db.xfrc = b->xfrc_env;
+  b->db.xfrc_stride = 6 * b->dm.nbody;
+  return 0;
+}
+
+extern "C" int dx_set_xfrc_env(dx_batch* b, const float* xfrc, int32_t env0, int32_t n) {
+  if (!b || !xfrc) return fail(DX_EINVAL, "null argument");
+  if (env0 < 0 || n < 0 || env0 + n > b->nenv) return fail(DX_EINVAL, "bad env range");
+  if (int rc = xfrc_env_mode(b)) return rc;
+  const size_t row = (size_t)b->dm.nbody * 6 * 4;
+  if (n > 0) HIPCHK(hipMemcpyAsync((char*)b->xfrc_env + (size_t)env0 * row, xfrc, (size_t)n * row, hipMemcpyDefault, b->stream));
+  return 0;
+}
+
+extern "C" int dx_get_xfrc_env(dx_batch* b, float* dst, int32_t env0, int32_t n) {
+  if (!b || !dst) return fail(DX_EINVAL, "null argument");
+  if (env0 < 0 || n < 0 || env0 + n > b->nenv) return fail(DX_EINVAL, "bad env range");
+  const size_t row = (size_t)b->dm.nbody * 6 * 4;
+  HIPCHK(hipSetDevice(b->device));
+  if (b->db.xfrc_stride) {
+    if (n > 0) HIPCHK(hipMemcpyAsync(dst, (char*)b->xfrc_env + (size_t)env0 * row, (size_t)n * row, hipMemcpyDefault, b->stream));
+  } else {  // shared mode: every env reads the shared array (zeros without one)
+    for (int k = 0; k < n; k++) HIPCHK(hipMemcpyAsync((char*)dst + k * row, b->xfrc, row, hipMemcpyDefault, b->stream));
+  }
+  HIPCHK(hipStreamSynchronize(b->stream));
+  return queue_check(b);
+}
+
+extern "C" int dx_xfrc_ptr(dx_batch* b, void** devptr, int32_t* stride) {
+  if (!b || !devptr) return fail(DX_EINVAL, "null argument");
+  if (!b->db.xfrc_stride) return fail(DX_EINVAL, "the batch's applied wrenches are shared (dx_set_xfrc_env switches to per-env rows)");
+  *devptr = b->xfrc_env;
+  if (stride) *stride = b->db.xfrc_stride;
   return 0;
 }
 
@@ -1918,6 +1974,12 @@ struct dx_env {
   ContactSense CF{};
   float* cf_out = nullptr;
   bool cf_on = false;
+  // the random pushes (dx_env_set_perturbation): off while PT.nb == 0; the buffers
+  // (PT.mt != nullptr once allocated, sized for DX_PERT_MAXB bodies) are the batch's;
+  // pt_shared: the batch had a shared xfrc array when the feature went on (restored when
+  // it goes off)
+  Perturb PT{};
+  bool pt_shared = false;
 };
 
 static void obs_pipe_free(ObsPipe& O) {
@@ -2155,6 +2217,13 @@ static int env_run(dx_env* e, const float* action, bool random = false, uint64_t
   dx_batch* b = e->batch;
   HIPCHK(hipSetDevice(b->device));
   if (e->H.mask & HOBS_NEEDS_BODIES) b->db.out_bodies = 1;  // (whatever dx_set_outputs was told since)
+  if (e->PT.nb && (action || random)) {
+    // the random pushes: one launch ahead of the step's, which then read the env's own xfrc
+    // rows (per-env mode again, from the current shared array, had dx_set_xfrc left it)
+    if (int rc = xfrc_env_mode(b)) return rc;
+    e->PT.xfrc = b->xfrc_env;
+    HIPCHK(dx_launch_perturb(b->stream, e->PT));
+  }
   if (e->F.flags && (action || random)) {
     // the action pipeline: one launch ahead of the step's, which then read the filtered
     // buffer (never the caller's); the random agent draws into the action buffer first --
@@ -2214,8 +2283,25 @@ static int env_run(dx_env* e, const float* action, bool random = false, uint64_t
   return env_observe(e);
 }
 
+// The pushes' initialize_episode for every env: no wrench held, every row the base again
+// (the per-env rows refilled from the shared array), nothing drawn.
+static int perturb_clear(dx_env* e) {
+  dx_batch* b = e->batch;
+  const size_t E = e->P.nenv;
+  HIPCHK(hipMemsetAsync(e->PT.remain, 0, E * DX_PERT_MAXB * 4, b->stream));
+  HIPCHK(hipMemsetAsync(e->PT.wrench, 0, E * DX_PERT_MAXB * 6 * 4, b->stream));
+  b->db.xfrc = e->pt_shared ? b->xfrc : nullptr;
+  b->db.xfrc_stride = 0;
+  return xfrc_env_mode(b);
+}
+
 extern "C" int dx_env_reset(dx_env* e) {
   if (!e) return fail(DX_EINVAL, "null env");
+  if (e->PT.nb) {
+    // (dx_set_xfrc on the env's batch since: that array is the base now)
+    if (!e->batch->db.xfrc_stride) e->pt_shared = e->batch->db.xfrc != nullptr;
+    if (int rc = perturb_clear(e)) return rc;
+  }
   // step_type LAST makes the pre-kernel run initialize_episode for every env
   std::vector<int> last(e->P.nenv, 2);
   HIPCHK(hipMemcpyAsync(e->S.step_type, last.data(), last.size() * 4, hipMemcpyHostToDevice, e->batch->stream));
@@ -2304,6 +2390,91 @@ extern "C" int dx_env_action_noise_draw(dx_env* e, int32_t n, double* out_host) 
   if (err == hipSuccess) err = hipStreamSynchronize(b->stream);
   (void)hipFree(dev);
   if (err != hipSuccess) return fail(DX_EHIP, std::string("action noise draw: ") + hipGetErrorString(err));
+  return 0;
+}
+
+// ------------------------------------------------------------------------ //
+// the random pushes (dx_perturb.hip dx_perturb_kernel)
+// ------------------------------------------------------------------------ //
+extern "C" int dx_env_set_perturbation(dx_env* e, const dx_perturbation* p) {
+  if (!e) return fail(DX_EINVAL, "null env");
+  dx_batch* b = e->batch;
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));  // may be called between steps
+  Perturb& T = e->PT;
+  if (!p || p->nbody == 0) {  // off: shared mode, the launches, outputs and checkpoint of an env never configured
+    if (T.nb) {
+      if (b->db.xfrc_stride) {  // (else dx_set_xfrc has already left per-env mode)
+        b->db.xfrc = e->pt_shared ? b->xfrc : nullptr;
+        b->db.xfrc_stride = 0;
+      }
+      T.nb = 0;
+    }
+    return 0;
+  }
+  // every check ahead of every change: a rejected call leaves everything as it was
+  if (e->P.kind == DX_KIND_REACH)
+    return fail(DX_EINVAL, "perturbation: not for the reach tasks (their goal rollouts step the physics inside the reset)");
+  if (p->nbody < 0) return fail(DX_EINVAL, "perturbation: negative body count");
+  if (p->nbody > DX_PERT_MAXB) return fail(DX_ELIMIT, "perturbation: more than 4 bodies");
+  for (int k = 0; k < p->nbody; k++) {
+    if (p->bodies[k] < 1 || p->bodies[k] >= b->dm.nbody)
+      return fail(DX_EINVAL, "perturbation: a body id outside [1, nbody) (the world body cannot be pushed)");
+    for (int j = 0; j < k; j++)
+      if (p->bodies[j] == p->bodies[k]) return fail(DX_EINVAL, "perturbation: a repeated body id");
+  }
+  if (!(p->probability >= 0.0 && p->probability <= 1.0)) return fail(DX_EINVAL, "perturbation: probability outside [0, 1]");
+  auto range_ok = [](double lo, double hi) { return std::isfinite(lo) && std::isfinite(hi) && lo >= 0.0 && lo <= hi; };
+  if (!range_ok(p->force_min, p->force_max)) return fail(DX_EINVAL, "perturbation: force range must be finite, non-negative, min <= max");
+  if (!range_ok(p->torque_min, p->torque_max)) return fail(DX_EINVAL, "perturbation: torque range must be finite, non-negative, min <= max");
+  if (p->duration < 1) return fail(DX_EINVAL, "perturbation: duration below one control step");
+  if (!T.nb && b->db.xfrc_stride)
+    return fail(DX_EINVAL, "perturbation: the env's batch already has per-env xfrc rows of the caller's (dx_set_xfrc_env)");
+  const size_t E = e->P.nenv;
+  if (!T.mt) {  // first use
+    Perturb A{};
+    int rc = balloc(b, (void**)&A.mt, E * DX_MTW_WORDS * 4);
+    if (!rc) rc = balloc(b, (void**)&A.remain, E * DX_PERT_MAXB * 4);
+    if (!rc) rc = balloc(b, (void**)&A.wrench, E * DX_PERT_MAXB * 6 * 4);
+    if (rc) return rc;
+    A.nenv = e->P.nenv;
+    A.nbody = b->dm.nbody;
+    A.step_type = e->S.step_type;
+    A.episode = e->S.episode;
+    A.base = b->xfrc;
+    T = A;
+  }
+  if (!T.nb || !b->db.xfrc_stride) e->pt_shared = b->db.xfrc != nullptr;
+  // env e draws from RandomState(seed + env0 + e)
+  hipLaunchKernelGGL(dx_mtw_seed_kernel, dim3((e->P.nenv + 63) / 64), dim3(64), 0, b->stream, e->P.nenv,
+                     p->seed + (uint64_t)e->P.env0, T.mt);
+  HIPCHK(hipGetLastError());
+  if (int rc = perturb_clear(e)) return rc;
+  HIPCHK(hipStreamSynchronize(b->stream));
+  for (int k = 0; k < DX_PERT_MAXB; k++) T.body[k] = k < p->nbody ? p->bodies[k] : 0;
+  T.prob = p->probability;
+  T.fmin = p->force_min; T.fmax = p->force_max;
+  T.tmin = p->torque_min; T.tmax = p->torque_max;
+  T.duration = p->duration;
+  T.xfrc = b->xfrc_env;
+  T.nb = p->nbody;
+  return 0;
+}
+
+extern "C" int dx_env_perturb_draw(dx_env* e, int32_t n, double* out_host) {
+  if (!e || !out_host) return fail(DX_EINVAL, "null argument");
+  if (!e->PT.nb) return fail(DX_EINVAL, "the perturbation is not enabled");
+  if (n < 1 || n > DX_WAVE) return fail(DX_EINVAL, "between 1 and 64 doubles per call");
+  dx_batch* b = e->batch;
+  HIPCHK(hipSetDevice(b->device));
+  double* dev = nullptr;
+  const size_t bytes = (size_t)e->P.nenv * n * 8;
+  HIPCHK(hipMalloc((void**)&dev, bytes));
+  hipError_t err = dx_launch_perturb_draw(b->stream, e->P.nenv, (int)n, e->PT.mt, dev);
+  if (err == hipSuccess) err = hipMemcpyAsync(out_host, dev, bytes, hipMemcpyDeviceToHost, b->stream);
+  if (err == hipSuccess) err = hipStreamSynchronize(b->stream);
+  (void)hipFree(dev);
+  if (err != hipSuccess) return fail(DX_EHIP, std::string("perturbation draw: ") + hipGetErrorString(err));
   return 0;
 }
 
@@ -2676,6 +2847,12 @@ static std::vector<StateField> env_state_fields(dx_env* e) {
   }
   // the contact forces' rows, while they are on (as the hand observables' rows above)
   if (e->cf_on) f.push_back({"contact_force", e->cf_out, E * 3 * e->cf_pads.size() * 4});
+  if (e->PT.nb) {  // the pushes' state, while they are on (their configuration is not saved)
+    const Perturb& T = e->PT;
+    f.push_back({"perturb_remain", T.remain, E * T.nb * 4});
+    f.push_back({"perturb_wrench", T.wrench, E * T.nb * 6 * 4});
+    f.push_back({"mt_perturb", T.mt, E * DX_MTW_WORDS * 4});
+  }
   return f;
 }
 
@@ -2756,6 +2933,10 @@ extern "C" int dx_env_output(dx_env* e, int which, void** devptr) {
     case DX_OUT_CONTACT_FORCE:
       if (!e->cf_on) return fail(DX_EINVAL, "no contact forces: dx_env_set_contact_forces has not enabled them");
       *devptr = e->cf_out;
+      return 0;
+    case DX_OUT_PERTURB:
+      if (!e->PT.nb) return fail(DX_EINVAL, "no pushes: dx_env_set_perturbation has not enabled them");
+      *devptr = e->PT.wrench;
       return 0;
   }
   return fail(DX_EINVAL, "unknown output");

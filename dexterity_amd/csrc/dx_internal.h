@@ -149,7 +149,10 @@ struct DevBatch {
   float *qpos, *qvel, *ctrl, *qacc_ws, *qacc, *time;
   float *site_xpos, *site_vel, *xpos, *xquat;
   int *ncon, *watch, *niter, *ncand;
-  const float* xfrc;  // [nbody*6], shared by all envs (may be null)
+  // applied wrenches (may be null): env e reads xfrc + e * xfrc_stride; stride 0 is one
+  // [nbody*6] array shared by all envs, 6*nbody per-env rows [nenv][nbody][6] (dx_set_xfrc_env)
+  const float* xfrc;
+  int xfrc_stride;
   int out_bodies;     // write DX_XPOS / DX_XQUAT after each step (dx_set_outputs)
   const int* skip;    // [nenv] nonzero: env was just reset, observe only (may be null)
   int watch_geom, watch_body;
@@ -370,6 +373,26 @@ struct ObsPipe {
   float* out;                    // DX_OUT_OBS_BUFFER: [nenv][K][W] oldest first, [nenv][W] with an aggregator
 };
 
+// The random pushes ahead of the step (dx_env_set_perturbation; dx_perturb.hip
+// dx_perturb_kernel): per configured body a held wrench and the control steps it still
+// lasts.  Like the pipelines above, its state belongs to the dx_env: the step kernels only
+// read the per-env xfrc rows it writes.
+#define DX_PERT_WAVES 4  // envs (one wave each) per workgroup
+#define DX_PERT_MAXB 4   // configured bodies (include/dx.h dx_perturbation::bodies)
+struct Perturb {
+  int nb;                // configured bodies; 0: off (nothing is launched)
+  int nenv, nbody;
+  int body[DX_PERT_MAXB];
+  int duration;          // control steps a push lasts
+  double prob, fmin, fmax, tmin, tmax;
+  const int *step_type, *episode;  // TaskState's, read before task_pre changes them
+  uint32_t* mt;          // [nenv][DX_MTW_WORDS] RandomState(seed + env0 + e)
+  int* remain;           // [nenv][nb] control steps the held wrench still lasts after this one
+  float* wrench;         // DX_OUT_PERTURB [nenv][nb][6] (force, torque), world frame at the body com
+  const float* base;     // the batch's shared xfrc [nbody][6] (zeros without one)
+  float* xfrc;           // the batch's per-env rows [nenv][nbody][6]
+};
+
 // numpy.random.RandomState-compatible MT19937 ([3P] numpy legacy seeding and
 // random_sample: mt19937_seed, mt19937_gen, legacy_double), one stream per env kept in
 // HBM interleaved over the envs -- word k of env e at k * nenv + e (k < 624), the read
@@ -542,3 +565,7 @@ hipError_t dx_launch_hand_obs(hipStream_t stream, const HandObs& H);
 // (restart: every env starts its history afresh from its current row), and its test hook
 hipError_t dx_launch_obs_pipe(hipStream_t stream, const ObsPipe& O, int restart);
 hipError_t dx_launch_obs_noise_draw(hipStream_t stream, int nenv, int n, uint32_t* mt, double* out);
+
+// dx_perturb.hip: the random pushes, queued ahead of the step's launches, and their test hook
+hipError_t dx_launch_perturb(hipStream_t stream, const Perturb& P);
+hipError_t dx_launch_perturb_draw(hipStream_t stream, int nenv, int n, uint32_t* mt, double* out);

@@ -78,7 +78,7 @@ extern "C" __global__ void __launch_bounds__(64) dx_sensor_kernel(const DevModel
     if (b >= 1) {
       const float* rc = rcom + 3 * m.body_rootidx[b];
       if (B.xfrc) {  // applied wrench at the body com (xfrc rows: force, torque)
-        const float* x6 = B.xfrc + 6 * b;
+        const float* x6 = B.xfrc + (size_t)env * B.xfrc_stride + 6 * b;
         const float off[3] = {xipos[3 * b] - rc[0], xipos[3 * b + 1] - rc[1], xipos[3 * b + 2] - rc[2]};
         float tq[3];
         cross3(tq, off, x6);
@@ -155,7 +155,7 @@ extern "C" __global__ void __launch_bounds__(64) dx_sensor_kernel(const DevModel
     cross_force(t3, cv, t2);
     for (int x = 0; x < 6; x++) f[x] = t1[x] + t3[x];
     if (B.xfrc) {  // applied wrench at the body com (xfrc rows: force, torque)
-      const float* x6 = B.xfrc + 6 * b;
+      const float* x6 = B.xfrc + (size_t)env * B.xfrc_stride + 6 * b;
       const float off[3] = {xipos[3 * b] - rc[0], xipos[3 * b + 1] - rc[1], xipos[3 * b + 2] - rc[2]};
       float tq[3];
       cross3(tq, off, x6);

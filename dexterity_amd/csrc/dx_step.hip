@@ -1813,7 +1813,7 @@ __device__ __forceinline__ void make_constraint(const Ctx& c) {
 // velocity stage: comVel, RNE (+ applied wrench), passive, actuation
 // ------------------------------------------------------------------------ //
 template <class Ctx>
-__device__ __forceinline__ void velocity_stage(const Ctx& c, const float* xfrc) {
+__device__ __forceinline__ void velocity_stage(const Ctx& c, const float* xfrc, int xfrc_stride, int env) {
   const DevModel& m = c.mdl();
   int nv = c.nv;
   float* qvel = c.f(c.L.qvel);
@@ -1899,7 +1899,9 @@ __device__ __forceinline__ void velocity_stage(const Ctx& c, const float* xfrc) 
       for (int x = 0; x < 6; x++) f[x] = t1[x] + t3[x];
       if (xfrc) {
         float f6[6];
-        for (int x = 0; x < 6; x++) f6[x] = xfrc[6 * b + x];
+        // the env's own rows (stride 0: the shared array); nenv * 6 nbody < 2^31
+        const float* x6 = xfrc + (env * xfrc_stride + 6 * b);
+        for (int x = 0; x < 6; x++) f6[x] = x6[x];
         if (f6[0] != 0 || f6[1] != 0 || f6[2] != 0 || f6[3] != 0 || f6[4] != 0 || f6[5] != 0) {
           const int rootidx = __float_as_int(m.body_rec[8 * b + 3].w);
           const float* rc = c.f(c.L.rcom) + 3 * rootidx;
@@ -3522,8 +3524,10 @@ __device__ __forceinline__ void solve(const Ctx& c) {
 
 #undef DX_LANE_GROUP
 #define DX_LANE_GROUP DX_LG_EULER
+// xfrc: the applied wrenches (null: none), env reading xfrc + env * xfrc_stride -- the
+// shared array (stride 0) or its own rows
 template <class Ctx>
-__device__ __forceinline__ void forward(const Ctx& c, const float* xfrc) {
+__device__ __forceinline__ void forward(const Ctx& c, const float* xfrc, int xfrc_stride, int env) {
   const DevModel& m = c.mdl();
   int nv = c.nv;
   // Stage order (LDS phases, see dx_api.hip layout): kinematics/com/crb and the
@@ -3539,7 +3543,7 @@ __device__ __forceinline__ void forward(const Ctx& c, const float* xfrc) {
   tendon_lengths(c, tp);
   crb_mass(c);
   stage_mark(c, ST_CRB);
-  velocity_stage(c, xfrc);
+  velocity_stage(c, xfrc, xfrc_stride, env);
   stage_mark(c, ST_VEL);
   // qacc_smooth = M^-1 qfrc_smooth (Cholesky)
   float* H = c.f(c.L.tsm);
@@ -3798,7 +3802,7 @@ __device__ __forceinline__ void reach_prep(const Ctx& c, const DevBatch& B, int 
       const float t0 = time;
       const int n0 = c.I[I_NSTEP];
       for (int s = 0; s < 2; s++) {  // JointStaticIsolator: two physics steps
-        forward(c, B.xfrc);
+        forward(c, B.xfrc, B.xfrc_stride, env);
         for (int i = LANE; i < c.nv; i += DX_WAVE) ws[i] = c.f(c.L.qacc)[i];
         SYNC();
         euler(c, &time);
@@ -4036,7 +4040,7 @@ __device__ __forceinline__ void health_check(const Ctx& c, const DevBatch& B, in
 // One physics step (mj_step): forward, warm start <- solved qacc, Euler, health check.
 template <class Ctx>
 __device__ __forceinline__ void env_substep(const Ctx& c, const DevBatch& B, float& time, int env, bool last) {
-  forward(c, B.xfrc);
+  forward(c, B.xfrc, B.xfrc_stride, env);
   if (c.I[I_DEFER]) return;  // (the state in LDS is still the one this physics step started from)
   if (last && B.sen_stash) sensor_stash(c, B, env);
   float* ws = c.f(c.L.v5);
@@ -4300,7 +4304,7 @@ __device__ __forceinline__ void step_body(const DevModel& m, const DevBatch& B, 
     if (mode == 0) {
       env_substep(c, B, time, env, s == steps - 1);
     } else {
-      forward(c, B.xfrc);
+      forward(c, B.xfrc, B.xfrc_stride, env);
       if (!c.I[I_DEFER]) {
         if (B.sen_stash) sensor_stash(c, B, env);
         health_check(c, B, env, time, false);
@@ -4600,7 +4604,7 @@ dx_step_hi_kernel(const DevModel* __restrict__ mp, DevBatch B, Lds L, int nsub) 
     ctx_bind_env(c, B, env);
     float time = env_begin(c, B, env, nullptr, true);
     if (e & DX_DEFER_FWD) {
-      forward(c, B.xfrc);
+      forward(c, B.xfrc, B.xfrc_stride, env);
       if (B.sen_stash) sensor_stash(c, B, env);
       health_check(c, B, env, time, false);
       env_finish(c, B, env, time);

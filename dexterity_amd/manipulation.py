@@ -170,6 +170,52 @@ def obs_pipeline_options(n_sub_steps: int, update_interval=None, buffer_size=1, 
     return m, d, K, _lib.OBS_AGG[aggregator], _lib.OBS_PAD[pad], sigma
 
 
+def perturbation_settings(task, bodies=("prop",), probability=0.0, force_range=(0.0, 0.0), torque_range=(0.0, 0.0),
+                          duration_steps=1, seed=0) -> dict:
+    """`GoalEnvironment.configure_perturbations`' arguments, checked and resolved against
+    `task` without touching the library: body names to ids ("prop" is the task's prop body),
+    ranges to (min, max) floats.  ValueError for anything include/dx.h dx_env_set_perturbation
+    would refuse."""
+    if task.kind == _lib.TASK_REACH:
+        raise ValueError("perturbations need a prop to push and a reset that does not step the physics: "
+                         "the reach tasks have neither")
+    names = [bodies] if isinstance(bodies, str) else list(bodies)
+    if not 1 <= len(names) <= _lib.PERTURB_MAX_BODIES:
+        raise ValueError(f"between 1 and {_lib.PERTURB_MAX_BODIES} bodies, got {len(names)}")
+    body_names = task.compiled.names["body"]
+    ids = []
+    for n in names:
+        if n == "prop":
+            ids.append(int(task.prop_body))
+        elif isinstance(n, str) and n in body_names:
+            ids.append(body_names.index(n))
+        else:
+            raise ValueError(f"unknown body {n!r}")
+    if any(i < 1 for i in ids):
+        raise ValueError("the world body cannot be pushed")
+    if len(set(ids)) != len(ids):
+        raise ValueError(f"a body is named twice: {names}")
+    probability = float(probability)
+    if not 0.0 <= probability <= 1.0:  # (false for a NaN too)
+        raise ValueError(f"probability must be within [0, 1], got {probability}")
+
+    def rng(name, r):
+        try:
+            lo, hi = (float(v) for v in r)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be a (min, max) pair, got {r!r}") from None
+        if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 <= lo <= hi):
+            raise ValueError(f"{name} must be finite with 0 <= min <= max, got {r!r}")
+        return lo, hi
+
+    force_range, torque_range = rng("force_range", force_range), rng("torque_range", torque_range)
+    duration_steps = _whole_number("duration_steps", duration_steps)
+    if duration_steps < 1:
+        raise ValueError(f"duration_steps must be at least 1, got {duration_steps}")
+    return dict(bodies=tuple(names), body_ids=tuple(ids), probability=probability, force_range=force_range,
+                torque_range=torque_range, duration_steps=duration_steps, seed=int(seed))
+
+
 def observation_layout(hand_nq: int, hand_nv: int, ntips: int, with_prop: bool, hand: str,
                        goal_dim: int = 4) -> "collections.OrderedDict[str, slice]":
     """Named slices of the flat observation vector written by dx_task_post_kernel."""
@@ -507,6 +553,8 @@ class GoalEnvironment:
         self._obs_pipe = None  # (row width W, delivered rows per env, aggregated)
         # enable_contact_forces: the pads of DX_OUT_CONTACT_FORCE (0: off)
         self.contact_force_pads = 0
+        # configure_perturbations' current settings (None: the random pushes are off)
+        self.perturbation_options = None
         if np.isfinite(self.time_limit):
             _lib.check(L.dx_env_set_time_limit(self.ptr, self.time_limit))
         # max_time_per_goal in fp64 (the params carry it as a float)
@@ -748,6 +796,52 @@ class GoalEnvironment:
         n = self.contact_force_pads
         return self._read(_lib.OUT_CONTACT_FORCE, np.float32, 3 * n).reshape(self.num_envs, n, 3)
 
+    # ---------------------------------------------------------------- random pushes
+    def configure_perturbations(self, bodies=("prop",), probability: float = 0.0, force_range=(0.0, 0.0),
+                                torque_range=(0.0, 0.0), duration_steps: int = 1, seed: Optional[int] = None) -> None:
+        """Random pushes on the device, ahead of every control step (include/dx.h
+        dx_env_set_perturbation): each of `bodies` (1 to 4 body names; "prop" is the task's
+        prop) starts a push with `probability` per control step while it holds none -- a force
+        of magnitude uniform in `force_range` (N) and a torque uniform in `torque_range` (N m),
+        both uniformly directed, world frame at the body's com -- and holds it for
+        `duration_steps` control steps.  Env e draws from RandomState(seed + env_offset + e),
+        `seed` defaulting to the env's.  `bodies=None` switches the feature off.  The pushes
+        are added to the gravity compensation in the env's own xfrc_applied rows;
+        `applied_perturbations()` reads them back.  A checkpoint carries the held pushes and
+        the streams but not these settings: load it into an env configured the same way.
+        The reach tasks refuse (ValueError)."""
+        L = _lib.load() if bodies is None else None
+        if bodies is None:
+            _lib.check(L.dx_env_set_perturbation(self.ptr, None))
+            self.perturbation_options = None
+            return
+        opt = perturbation_settings(self.task, bodies, probability, force_range, torque_range, duration_steps,
+                                    self._seed if seed is None else seed)
+        p = _lib.Perturbation()
+        p.nbody = len(opt["body_ids"])
+        for k, b in enumerate(opt["body_ids"]):
+            p.bodies[k] = b
+        p.probability = opt["probability"]
+        p.force_min, p.force_max = opt["force_range"]
+        p.torque_min, p.torque_max = opt["torque_range"]
+        p.duration = opt["duration_steps"]
+        p.seed = opt["seed"] & (2**64 - 1)
+        _lib.check(_lib.load().dx_env_set_perturbation(self.ptr, ctypes.byref(p)))
+        self.perturbation_options = opt
+
+    def applied_perturbations_ptr(self) -> int:
+        """Device address of the [num_envs, nb, 6] float32 pushes (while configured)."""
+        return self._out(_lib.OUT_PERTURB)
+
+    def applied_perturbations(self) -> np.ndarray:
+        """[num_envs, nb, 6] float32 host copy of DX_OUT_PERTURB: per configured body the
+        (force, torque) the last control step applied on top of the gravity compensation;
+        zeros on FIRST steps and after `reset` (DxError while off)."""
+        if self.perturbation_options is None:
+            raise _lib.DxError("perturbations are off (configure_perturbations)")
+        nb = len(self.perturbation_options["body_ids"])
+        return self._read(_lib.OUT_PERTURB, np.float32, 6 * nb).reshape(self.num_envs, nb, 6)
+
     # ---------------------------------------------------------------- observation pipeline
     def _row_layout(self) -> "collections.OrderedDict[str, slice]":
         """Named slices of the pipeline's row: the observation, then the hand observables."""
@@ -826,7 +920,8 @@ class GoalEnvironment:
                      "nsub_d": np.int32, "solve_n": np.int32, "mt_env": np.uint32, "mt_goal": np.uint32,
                      "mt_reach": np.uint32, "step_cost": np.uint32, "order": np.int32,
                      "act_ema_set": np.int32, "mt_noise": np.uint32,
-                     "obs_count": np.int32, "mt_obs_noise": np.uint32}
+                     "obs_count": np.int32, "mt_obs_noise": np.uint32,
+                     "perturb_remain": np.int32, "mt_perturb": np.uint32}
 
     def _state_fields(self):
         L = _lib.load()
@@ -885,6 +980,9 @@ class GoalEnvironment:
             if ("contact_force" in z.files) != ("contact_force" in {name for name, _, _ in fields}):
                 raise ValueError("checkpoint and env differ in the contact forces (on in one, off in the other): "
                                  "enable_contact_forces as the saved env did, then load")
+            if ("mt_perturb" in z.files) != ("mt_perturb" in {name for name, _, _ in fields}):
+                raise ValueError("checkpoint and env differ in the perturbations (on in one, off in the other): "
+                                 "configure_perturbations as the saved env was, then load")
             nbytes = sum(nb for _, _, nb in fields)
             buf = np.empty(nbytes, dtype=np.uint8)
             for name, off, nb in fields:

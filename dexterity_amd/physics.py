@@ -114,13 +114,42 @@ class BatchedPhysics:
         _lib.check(_lib.load().dx_field_ptr(self.ptr, field, ctypes.byref(p)))
         return p.value
 
-    def set_xfrc(self, xfrc) -> None:
-        a = None if xfrc is None else np.ascontiguousarray(xfrc, dtype=np.float32).reshape(-1, 6)
-        if a is None:
+    def set_xfrc(self, xfrc, env0: int = 0) -> None:
+        """xfrc_applied: None (none) or [nbody, 6] -- one array shared by every env -- or
+        [n, nbody, 6], every env its own rows as in MjData (envs env0 .. env0+n-1; the batch
+        then stays in per-env mode until a shared array or None is set again)."""
+        nbody = self.model.nbody
+        if xfrc is None:
             _lib.check(_lib.load().dx_set_xfrc(self.ptr, None, 0))
+            self.sync()
+            return
+        a = np.ascontiguousarray(xfrc, dtype=np.float32)
+        if a.shape == (nbody, 6):
+            _lib.check(_lib.load().dx_set_xfrc(self.ptr, a.ctypes.data, nbody))
+        elif a.ndim == 3 and a.shape[1:] == (nbody, 6) and 1 <= a.shape[0] and 0 <= env0 and env0 + a.shape[0] <= self.nenv:
+            _lib.check(_lib.load().dx_set_xfrc_env(self.ptr, a.ctypes.data, env0, a.shape[0]))
         else:
-            _lib.check(_lib.load().dx_set_xfrc(self.ptr, a.ctypes.data, a.shape[0]))
-        self.sync()
+            raise ValueError(f"xfrc must be [nbody, 6] = [{nbody}, 6] or [n, {nbody}, 6] with env0 + n <= nenv = "
+                             f"{self.nenv}, got {a.shape} at env0 = {env0}")
+        self.sync()  # host buffer must outlive the async copy
+
+    @property
+    def xfrc_applied(self) -> np.ndarray:
+        """A host copy of the applied wrenches, shaped by the current mode: [nbody, 6] while
+        one array is shared (zeros while none is set), [nenv, nbody, 6] in per-env mode."""
+        per_env = self.xfrc_ptr() is not None
+        n = self.nenv if per_env else 1
+        out = np.empty((n, self.model.nbody, 6), np.float32)
+        _lib.check(_lib.load().dx_get_xfrc_env(self.ptr, out.ctypes.data, 0, n))
+        return out if per_env else out[0]
+
+    def xfrc_ptr(self) -> Optional[int]:
+        """Device address of the per-env rows [nenv, nbody, 6] f32 (write them on the batch's
+        stream; no host trip), or None while the batch shares one array."""
+        p, stride = ctypes.c_void_p(), ctypes.c_int32()
+        if _lib.load().dx_xfrc_ptr(self.ptr, ctypes.byref(p), ctypes.byref(stride)) < 0:
+            return None
+        return p.value
 
     def set_watch(self, geom: int, body: int) -> None:
         _lib.check(_lib.load().dx_set_watch(self.ptr, geom, body))

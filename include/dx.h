@@ -123,9 +123,27 @@ int dx_set_field(dx_batch* b, int field, const void* src, int32_t env0, int32_t 
 int dx_get_field(dx_batch* b, int field, void* dst, int32_t env0, int32_t n);
 /* Device pointer of a field's [nenv][width] array (zero-copy access). */
 int dx_field_ptr(dx_batch* b, int field, void** devptr);
-/* Batch-shared applied body wrench xfrc_applied[nbody][6] (force, torque), the
- * gravity-compensation write of utils/mujoco_utils.py:91-99. */
+/* Applied body wrenches, MuJoCo's d->xfrc_applied: per body (force, torque) in the world
+ * frame at the body's com.  A batch holds them in one of two modes.
+ *  shared   one xfrc_applied[nbody][6] read by every env: dx_set_xfrc, the
+ *    gravity-compensation write of utils/mujoco_utils.py:91-99 (NULL: none).  The default.
+ *  per-env  rows [nenv][nbody][6], every env its own as in MjData: dx_set_xfrc_env writes
+ *    rows [n][nbody][6] for envs env0 .. env0+n-1 from host or device memory (as
+ *    dx_set_field).  The call that leaves shared mode first gives every env the shared
+ *    array's rows (zeros when none is set), so envs outside [env0, env0+n) keep what they
+ *    had been reading.  The step's arithmetic is the same in both modes: per-env rows that
+ *    all equal the shared array give the shared mode's bits.
+ * dx_set_xfrc (an array, or NULL) returns the batch to shared mode.  dx_get_xfrc_env reads
+ * back what env0 .. env0+n-1 read, in either mode (it synchronises the stream).
+ * dx_xfrc_ptr gives the per-env rows' device address and the stride between two envs in
+ * floats (6 * nbody; stride may be null) for writes from device code on dx_stream, and
+ * DX_EINVAL in shared mode.  dx_reset does not touch applied wrenches in either mode
+ * (mj_resetData zeroes them; here the gravity compensation is set once and must survive
+ * every reset, and the per-env rows follow the same rule). */
 int dx_set_xfrc(dx_batch* b, const float* xfrc, int32_t nbody);
+int dx_set_xfrc_env(dx_batch* b, const float* xfrc, int32_t env0, int32_t n);
+int dx_get_xfrc_env(dx_batch* b, float* dst, int32_t env0, int32_t n);
+int dx_xfrc_ptr(dx_batch* b, void** devptr, int32_t* stride);
 /* Geom whose contacts set DX_GROUND_CONTACT (-1 disables). */
 int dx_set_ground_geom(dx_batch* b, int32_t geom);
 /* DX_GROUND_CONTACT watches contacts between `geom` and any geom of `body`
@@ -273,7 +291,10 @@ enum dx_env_out { DX_OUT_OBS = 0, DX_OUT_REWARD = 1, DX_OUT_DISCOUNT = 2, DX_OUT
                                             aggregator: the observation pipeline's delivered rows;
                                             while it is on (below) */,
                   DX_OUT_CONTACT_FORCE = 11 /* [nenv][3 * npad] f32, the contact forces of the task's
-                                               pads; while they are on (below) */ };
+                                               pads; while they are on (below) */,
+                  DX_OUT_PERTURB = 12 /* [nenv][nb][6] f32, the random pushes' wrenches (force,
+                                         torque) on the nb configured bodies; while they are on
+                                         (below) */ };
 dx_env* dx_env_create(const dx_model* m, int32_t nenv, int32_t device, int32_t task, uint64_t seed,
                       const float* params, int32_t nparams);
 /* One shard of a job's environments: this handle's env e is the job's env env0 + e.
@@ -424,6 +445,59 @@ int dx_env_hand_obs_dim(const dx_env* e);
 int dx_env_set_contact_forces(dx_env* e, int enable);
 int dx_env_contact_force_dim(const dx_env* e);
 int dx_env_contact_force_bodies(const dx_env* e, int32_t* out, int32_t n);
+
+/* Random pushes: the third part of the robustness kit beside the action noise and the
+ * observation pipeline -- random wrenches on the prop (or up to four bodies), on the device:
+ * one small kernel ahead of every control step (dx_env_step, dx_env_step_host,
+ * dx_env_step_random), beside the action filter's, that writes the env's own xfrc_applied
+ * rows.  While the feature is on the env's batch runs in per-env xfrc mode (above).
+ * Env e owns a numpy-compatible RandomState(seed + env0 + e) of its own, keyed by the
+ * job-wide env index: replayable from numpy, a shard equals the unsharded batch, no other
+ * stream moves.  Per (env, configured body) the state is `remain` (int32) and `wrench`
+ * (fp32 [6]: force, torque; world frame at the body's com, xfrc_applied's convention).
+ * Per control step, for each configured body in order, exactly seven random_sample
+ * doubles are drawn -- u_gate, u_fmag, u_fz, u_fphi, u_tmag, u_tz, u_tphi -- whichever
+ * rule then applies.  Draws that go unused are intended: a step's consumption is fixed, so
+ * a replay is one random_sample(7 * nb) per step.  The first rule that matches:
+ *  - the step re-initialises the env (it returns FIRST): remain = 0, wrench = 0;
+ *  - remain > 0: remain -= 1, the wrench is kept;
+ *  - else wrench = 0, and if u_gate < probability: remain = duration - 1 and
+ *      force  = (force_min + (force_max - force_min) u_fmag) * dir(u_fz, u_fphi),
+ *      torque = (torque_min + (torque_max - torque_min) u_tmag) * dir(u_tz, u_tphi),
+ *      dir(u_z, u_phi) = (s cos phi, s sin phi, z), z = 2 u_z - 1, s = sqrt(1 - z z),
+ *      phi = 2 pi u_phi (uniform on the sphere); fp64 without contraction, each component
+ *      magnitude * direction rounded to fp32 once.
+ * A push therefore lasts exactly `duration` control steps (every physics step of them), and
+ * a new one can start on the step after one ends.  The kernel writes xfrc[e][body] =
+ * base[body] + wrench, one fp32 add per component, base being the batch's shared array (the
+ * gravity compensation; dx_set_xfrc on the env's batch while the feature is on replaces the
+ * base), and DX_OUT_PERTURB [nenv][nb][6], a library-owned buffer holding the wrench.
+ * dx_env_reset clears the state (zero wrenches, rows = base) and draws nothing.
+ * dx_env_set_perturbation may be called between steps (it synchronises the stream); an
+ * accepted call seeds the streams and clears the state.  NULL or nbody == 0 switches the
+ * feature off (the default): the batch returns to shared mode, and the step's launches,
+ * every output and the checkpoint are those of an env never configured;
+ * dx_env_output(DX_OUT_PERTURB) fails.  While on, the checkpoint carries the state after the
+ * other optional fields -- perturb_remain (int32), perturb_wrench, mt_perturb -- but not
+ * this configuration: load into an env configured the same way.
+ * A rejected call changes nothing.  DX_EINVAL: a body id outside [1, nbody) (the world body
+ * cannot be pushed) or repeated; probability outside [0, 1]; a negative or non-finite range
+ * or min > max; duration < 1; a batch already put in per-env xfrc mode by the caller; the
+ * reach tasks (their goal rollouts step the physics inside the reset, so a push would
+ * change the goal sampling).  DX_ELIMIT: more than 4 bodies. */
+typedef struct dx_perturbation {
+  int32_t nbody;          /* 1..4 configured bodies; 0: off */
+  int32_t bodies[4];      /* body ids, never the world body (0) */
+  double probability;     /* of a new push per control step and body, while none is held */
+  double force_min, force_max;    /* N */
+  double torque_min, torque_max;  /* N m */
+  int32_t duration;       /* control steps, >= 1 */
+  uint64_t seed;
+} dx_perturbation;
+int dx_env_set_perturbation(dx_env* e, const dx_perturbation* p);
+/* Test hook: the next n (1..64) random_sample doubles of every env's push stream, consumed;
+ * out_host [nenv][n] f64.  The feature must be on. */
+int dx_env_perturb_draw(dx_env* e, int32_t n, double* out_host);
 
 /* The observation pipeline: the options the reference gives every observable
  * (ObservableSpec, manipulation/shared/observations.py:8-17, handed on by make_options
