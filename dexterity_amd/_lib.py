@@ -46,6 +46,8 @@ EXPORTS = (
     "dx_contact_enable", "dx_contact_set_pads", "dx_contact_npad",
     "dx_env_set_contact_forces", "dx_env_contact_force_dim", "dx_env_contact_force_bodies",
     "dx_set_xfrc_env", "dx_get_xfrc_env", "dx_xfrc_ptr", "dx_env_set_perturbation", "dx_env_perturb_draw",
+    "dx_model_hull_planes", "dx_render_set_cameras", "dx_render", "dx_render_output", "dx_render_get",
+    "dx_render_stats", "dx_ray", "dx_env_set_cameras",
 )
 COMM_ID_BYTES = 128
 STAGES = ("kinematics", "crb", "broadphase", "midphase", "narrowphase", "constraints", "velocity",
@@ -67,6 +69,9 @@ OUT_OBS_BUFFER = 10
 OUT_CONTACT_FORCE = 11
 OUT_PERTURB = 12
 PERTURB_MAX_BODIES = 4
+OUT_DEPTH, OUT_SEGMENTATION = 13, 14
+RENDER_DEPTH, RENDER_SEGMENTATION, RENDER_NO_CULL = 1, 2, 4  # dx_render_set_cameras flags / dx_render_output
+RENDER_MAX_CAMERAS, RENDER_MAX_SIDE = 8, 512
 # dx_obs_pipeline.padding / .aggregator, by composer's names
 OBS_PAD = {"zero": 0, "initial_value": 1}
 OBS_AGG = {None: 0, "min": 1, "max": 2, "mean": 3, "median": 4, "sum": 5}
@@ -148,6 +153,19 @@ class Perturbation(ctypes.Structure):
         ("torque_max", ctypes.c_double),
         ("duration", ctypes.c_int32),
         ("seed", ctypes.c_uint64),
+    ]
+
+
+class Camera(ctypes.Structure):
+    """struct dx_camera (include/dx.h)."""
+
+    _fields_ = [
+        ("pos", ctypes.c_float * 3),
+        ("xyaxes", ctypes.c_float * 6),
+        ("fovy", ctypes.c_float),
+        ("near_", ctypes.c_float),
+        ("far_", ctypes.c_float),
+        ("body", ctypes.c_int32),
     ]
 
 
@@ -252,6 +270,15 @@ def load(path: str = LIB_PATH):
         L.dx_xfrc_ptr.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(i32)]
         L.dx_env_set_perturbation.argtypes = [vp, ctypes.POINTER(Perturbation)]
         L.dx_env_perturb_draw.argtypes = [vp, i32, vp]
+    if hasattr(L, "dx_render_set_cameras"):  # (an older variant library for A/B lacks the cameras)
+        L.dx_model_hull_planes.argtypes = [vp, i32, vp, i32]
+        L.dx_render_set_cameras.argtypes = [vp, vp, i32, i32, i32, i32]
+        L.dx_render.argtypes = [vp]
+        L.dx_render_output.argtypes = [vp, ctypes.c_int, ctypes.POINTER(vp)]
+        L.dx_render_get.argtypes = [vp, ctypes.c_int, vp, i32, i32]
+        L.dx_render_stats.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
+        L.dx_ray.argtypes = [vp, vp, vp, i32, vp, vp]
+        L.dx_env_set_cameras.argtypes = [vp, vp, i32, i32, i32, i32]
     L.dx_timing_enable.argtypes = [vp, ctypes.c_int]
     L.dx_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i32)]
     L.dx_stage_timing.argtypes = [vp, ctypes.c_int]

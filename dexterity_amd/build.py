@@ -22,7 +22,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libdx.so")
 SPECS = os.path.join(CSRC, "dx_specs.inc")
 SOURCES = ("dx_step.hip", "dx_ik.hip", "dx_dls.hip", "dx_task.hip", "dx_sensor.hip", "dx_observe.hip", "dx_obspipe.hip",
-           "dx_perturb.hip", "dx_api.hip")
+           "dx_perturb.hip", "dx_render.hip", "dx_api.hip")
 HEADERS = ("dx_internal.h", "dx_device.h", "dx_jac.h", "dx_task.h", "dx_mtw.h")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 DIMS = ("nq", "nv", "nbody", "njnt", "nu", "ntendon", "nsite", "nlevel", "nroot", "nfric", "nlimj", "nlimt",

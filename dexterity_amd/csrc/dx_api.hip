@@ -16,6 +16,7 @@
 #include <array>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -85,6 +86,14 @@ struct dx_model {
   Lds lds_hi;  // the overflow tier's (DX_NCON_HI)
   Lds lds_mid; // the mid tier's (DX_NCON_MID; nefc_max 0: not available for this model)
   int ncon_max, nefc_max;
+  // hull face planes (hull_planes below), derived when cameras or rays are first used:
+  // plane4 [nplane][4] = (n, d) with n x + d <= 0 inside, hull k's run at planeadr[k],
+  // planenum[k]; render_dev: their device copies per device
+  bool planes_built = false;
+  std::vector<float> plane4;
+  std::vector<int> planeadr, planenum;
+  struct RenderDev { const float4* plane4; const int *planeadr, *planenum; };
+  std::map<int, RenderDev> render_dev;
 };
 
 static int geti(const dx_model* m, const char* name, int def = -1) {
@@ -905,6 +914,128 @@ extern "C" int dx_hull_support(const dx_model* m, int32_t mesh, const float dir[
   return 0;
 }
 
+// Hull face planes for the ray cast (dx_render.hip).  The blob carries a hull's vertices and
+// the vertex adjacency, no faces.  For a vertex i and two of its neighbours j, k that are
+// neighbours of each other (i < j < k: every triangle once), the plane through the three is
+// a face when every hull vertex lies on one side of it, to 1e-9 max|v|; it is oriented
+// outward and stored as unit (n, d), n x + d <= 0 inside.  Coplanar triangles (a polygonal
+// face's fan) merge into one plane.  fp64 on the blob's fp64 vertices, rounded once.
+static std::recursive_mutex g_render_mu;  // the plane table and its per-device copies
+static int hull_planes(dx_model* m) {
+  std::lock_guard<std::recursive_mutex> lock(g_render_mu);
+  if (m->planes_built) return 0;
+  const auto& vadr = m->hi.at("mesh_vertadr");
+  const auto& vnum = m->hi.at("mesh_vertnum");
+  const int nmesh = (int)vnum.size();
+  m->planeadr.assign(std::max(nmesh, 1), 0);
+  m->planenum.assign(std::max(nmesh, 1), 0);
+  m->plane4.clear();
+  auto iv = m->arr.find("mesh_vert");
+  auto ia = m->arr.find("mesh_vertadj");
+  auto ij = m->arr.find("mesh_adj");
+  if (nmesh > 0 && (iv == m->arr.end() || ia == m->arr.end() || ij == m->arr.end() || iv->second.dtype != 1 ||
+                    ia->second.dtype != 0 || ij->second.dtype != 0))
+    return fail(DX_EMODEL, "hull planes: the blob lacks mesh_vert / mesh_vertadj / mesh_adj");
+  for (int k = 0; k < nmesh; k++) {
+    const int nv = vnum[k], base = vadr[k];
+    if (base < 0 || (long)(base + nv) * 3 > iv->second.n || (long)(base + nv) * 2 > ia->second.n)
+      return fail(DX_EMODEL, "hull planes: mesh vertex range outside the blob's arrays");
+    const double* V = (const double*)iv->second.p + 3 * (size_t)base;
+    const int* VA = (const int*)ia->second.p + 2 * (size_t)base;
+    const int* ADJ = (const int*)ij->second.p;
+    const long nadj = ij->second.n;
+    double R = 0;
+    for (int i = 0; i < 3 * nv; i++) R = std::max(R, std::fabs(V[i]));
+    const double tol = 1e-9 * R;
+    // two planes merge when their unit normals agree to kMerge per component and their
+    // offsets to kMerge R: the meshes' vertices are float32 data, so a polygonal face's
+    // triangles are coplanar only to ~1e-7; the first one met stands for the face (a shift
+    // of at most 1e-6 R, below what the fp32 ray cast resolves)
+    const double kMerge = 1e-6;
+    std::vector<std::array<double, 4>> planes;
+    for (int i = 0; i < nv; i++) {
+      const int s = VA[2 * i], c = VA[2 * i + 1];
+      if (s < 0 || c < 0 || (long)s + c > nadj) return fail(DX_EMODEL, "hull planes: adjacency outside the blob's array");
+      for (int a = 0; a < c; a++) {
+        const int j = ADJ[s + a];
+        if (j <= i || j >= nv) continue;
+        const int sj = VA[2 * j], cj = VA[2 * j + 1];
+        if (sj < 0 || cj < 0 || (long)sj + cj > nadj) return fail(DX_EMODEL, "hull planes: adjacency outside the blob's array");
+        for (int b2 = 0; b2 < c; b2++) {
+          const int k2 = ADJ[s + b2];
+          if (k2 <= j || k2 >= nv) continue;
+          bool adj = false;
+          for (int q = 0; q < cj && !adj; q++) adj = ADJ[sj + q] == k2;
+          if (!adj) continue;
+          const double* p0 = V + 3 * i; const double* p1 = V + 3 * j; const double* p2 = V + 3 * k2;
+          const double e1[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
+          const double e2[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
+          double n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+          const double len = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+          if (!(len > 1e-14 * R * R)) continue;  // a degenerate triple
+          for (double& x : n) x /= len;
+          double d = -(n[0] * p0[0] + n[1] * p0[1] + n[2] * p0[2]);
+          double lo = 0, hi = 0;
+          for (int v = 0; v < nv; v++) {
+            const double sd = n[0] * V[3 * v] + n[1] * V[3 * v + 1] + n[2] * V[3 * v + 2] + d;
+            lo = std::min(lo, sd);
+            hi = std::max(hi, sd);
+          }
+          if (hi > tol && lo < -tol) continue;  // vertices on both sides: not a face
+          if (hi > tol) { for (double& x : n) x = -x; d = -d; }
+          bool dup = false;
+          for (const auto& P : planes)
+            if (std::fabs(P[0] - n[0]) < kMerge && std::fabs(P[1] - n[1]) < kMerge && std::fabs(P[2] - n[2]) < kMerge &&
+                std::fabs(P[3] - d) < kMerge * std::max(R, 1e-300)) { dup = true; break; }
+          if (!dup) planes.push_back({n[0], n[1], n[2], d});
+        }
+      }
+    }
+    m->planeadr[k] = (int)(m->plane4.size() / 4);
+    m->planenum[k] = (int)planes.size();
+    for (const auto& P : planes)
+      for (int q = 0; q < 4; q++) m->plane4.push_back((float)P[q]);
+  }
+  m->planes_built = true;
+  return 0;
+}
+
+extern "C" int dx_model_hull_planes(const dx_model* mc, int32_t mesh, float* out, int32_t n) {
+  dx_model* m = const_cast<dx_model*>(mc);
+  if (!m) return fail(DX_EINVAL, "null model");
+  if (mesh < 0 || mesh >= (int)m->hi.at("mesh_vertnum").size()) return fail(DX_EINVAL, "mesh out of range");
+  if (int rc = hull_planes(m)) return rc;
+  const int cnt = m->planenum[mesh];
+  if (out && n > 0)
+    memcpy(out, m->plane4.data() + 4 * (size_t)m->planeadr[mesh], (size_t)std::min(n, cnt) * 16);
+  return cnt;
+}
+
+// The plane table on `device`, uploaded once (freed with the model).
+static int render_tables(dx_model* m, int device, dx_model::RenderDev* out) {
+  // (batches of one model on several devices may first use cameras from different threads)
+  std::lock_guard<std::recursive_mutex> lock(g_render_mu);
+  if (int rc = hull_planes(m)) return rc;
+  auto it = m->render_dev.find(device);
+  if (it != m->render_dev.end()) { *out = it->second; return 0; }
+  std::vector<void*>& allocs = m->dev_allocs[device];
+  auto up = [&](const void* src, size_t bytes, const void** dst) -> int {
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, std::max<size_t>(bytes, 16)));
+    allocs.push_back(p);
+    if (bytes) HIPCHK(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
+    *dst = p;
+    return 0;
+  };
+  dx_model::RenderDev r{};
+  if (int rc = up(m->plane4.data(), m->plane4.size() * 4, (const void**)&r.plane4)) return rc;
+  if (int rc = up(m->planeadr.data(), m->planeadr.size() * 4, (const void**)&r.planeadr)) return rc;
+  if (int rc = up(m->planenum.data(), m->planenum.size() * 4, (const void**)&r.planenum)) return rc;
+  m->render_dev[device] = r;
+  *out = r;
+  return 0;
+}
+
 // Layout export for build.py's kernel specialization: the Lds struct (words, in
 // declaration order) followed by the 18 dimensions of dx_device.h DX_DIMS.
 extern "C" int dx_model_layout(const dx_model* m, int32_t* out, int32_t n) {
@@ -1050,6 +1181,17 @@ struct dx_batch {
   bool mid = false;
   hipStream_t side = nullptr;
   unsigned qdone_target = 0;
+  // cameras (dx_render_set_cameras): off while RA.ncam == 0; the images are the batch's,
+  // grown when a configuration needs more (rnd_cap pixels each); rnd_prev_bodies is the
+  // body-pose setting from before the cameras switched it on (-1: not switched)
+  RenderArgs RA{};
+  int rnd_flags = 0;
+  float* rnd_depth = nullptr;
+  int* rnd_seg = nullptr;
+  size_t rnd_depth_cap = 0, rnd_seg_cap = 0;
+  int rnd_prev_bodies = -1;
+  unsigned long long* rnd_stats = nullptr;
+  bool rnd_stats_on = false;
 };
 
 #define DX_HI_GRID 32  // workgroups of the overflow tier (each loops over the deferred steps)
@@ -1780,6 +1922,214 @@ extern "C" int dx_dls_map(dx_batch* b, const int32_t* types, const int32_t* ids,
   return 0;
 }
 
+// ------------------------------------------------------------------------ //
+// cameras and rays (dx_render.hip)
+// ------------------------------------------------------------------------ //
+// The model tables and the batch's poses every render / ray launch reads.
+static int render_base(dx_batch* b, RenderArgs& A) {
+  dx_model::RenderDev T;
+  if (int rc = render_tables(b->model, b->device, &T)) return rc;
+  const DevModel& d = b->dm;
+  A.nenv = b->nenv; A.ngeom = d.ngeom; A.nbody = d.nbody;
+  A.xpos = b->db.xpos; A.xquat = b->db.xquat;
+  A.geom_type = d.geom_type; A.geom_bodyid = d.geom_bodyid; A.geom_dataid = d.geom_dataid;
+  A.geom_size = d.geom_size; A.geom_pos = d.geom_pos; A.geom_mat = d.geom_mat; A.geom_bsphere = d.geom_bsphere;
+  A.mesh_planeadr = (decltype(A.mesh_planeadr))T.planeadr;
+  A.mesh_planenum = (decltype(A.mesh_planenum))T.planenum;
+  A.plane4 = (decltype(A.plane4))T.plane4;
+  return 0;
+}
+
+// A camera's frame from xyaxes, in fp64: x normalised, y made orthogonal to x and
+// normalised, z = x (x) y.  False: degenerate axes.
+static bool camera_frame(const dx_camera& c, RenderCam& out, int height) {
+  double x[3] = {c.xyaxes[0], c.xyaxes[1], c.xyaxes[2]}, y[3] = {c.xyaxes[3], c.xyaxes[4], c.xyaxes[5]};
+  for (int k = 0; k < 6; k++)
+    if (!std::isfinite(c.xyaxes[k])) return false;
+  const double nx = std::sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+  if (!(nx > 1e-10)) return false;
+  for (double& v : x) v /= nx;
+  const double dot = x[0] * y[0] + x[1] * y[1] + x[2] * y[2];
+  for (int k = 0; k < 3; k++) y[k] -= dot * x[k];
+  const double ny = std::sqrt(y[0] * y[0] + y[1] * y[1] + y[2] * y[2]);
+  if (!(ny > 1e-10)) return false;
+  for (double& v : y) v /= ny;
+  const double z[3] = {x[1] * y[2] - x[2] * y[1], x[2] * y[0] - x[0] * y[2], x[0] * y[1] - x[1] * y[0]};
+  for (int k = 0; k < 3; k++) {
+    out.pos[k] = c.pos[k];
+    out.x[k] = (float)x[k]; out.y[k] = (float)y[k]; out.z[k] = (float)z[k];
+  }
+  out.f = (float)(0.5 * height / std::tan(0.5 * (double)c.fovy * 3.14159265358979323846 / 180.0));
+  out.near_ = c.near_;
+  out.far_ = c.far_;
+  out.body = c.body;
+  return true;
+}
+
+// A buffer of at least `words` words for a new configuration: the current one when it is
+// large enough, else a fresh allocation (*fresh).  Nothing is freed here: the caller swaps
+// the fresh buffers in, and frees the ones they replace, only once every step has
+// succeeded, so a failed call leaves the active configuration and its images as they were.
+static int render_buffer(dx_batch* b, void* cur, size_t cap, size_t words, void** out, bool* fresh) {
+  *fresh = false;
+  *out = cur;
+  if (cap >= words) return 0;
+  void* p = nullptr;
+  if (hipMalloc(&p, std::max<size_t>(words * 4, 4)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(DX_ENOMEM, "cameras: image allocation failed");
+  }
+  if (hipMemsetAsync(p, 0, words * 4, b->stream) != hipSuccess) {
+    (void)hipFree(p);
+    return fail(DX_EHIP, "cameras: image clear failed");
+  }
+  *out = p;
+  *fresh = true;
+  return 0;
+}
+static void render_adopt(dx_batch* b, void** slot, size_t* cap, void* fresh, size_t words) {
+  if (*slot) {
+    (void)hipFree(*slot);
+    b->allocs.erase(std::remove(b->allocs.begin(), b->allocs.end(), *slot), b->allocs.end());
+  }
+  *slot = fresh;
+  *cap = words;
+  b->allocs.push_back(fresh);
+}
+
+extern "C" int dx_render_set_cameras(dx_batch* b, const dx_camera* cams, int32_t ncam, int32_t width, int32_t height,
+                                     int32_t flags) {
+  if (!b) return fail(DX_EINVAL, "null batch");
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));  // may be called between steps
+  if (ncam == 0) {  // off: nothing is launched, the buffers stay for a later call
+    b->RA.ncam = 0;
+    b->rnd_flags = 0;
+    if (b->rnd_prev_bodies >= 0) b->db.out_bodies = b->rnd_prev_bodies;
+    b->rnd_prev_bodies = -1;
+    return 0;
+  }
+  if (!cams || ncam < 0) return fail(DX_EINVAL, "cameras: null camera array or negative count");
+  if (width < 1 || height < 1) return fail(DX_EINVAL, "cameras: width and height must be positive");
+  if (flags & ~(DX_RENDER_DEPTH | DX_RENDER_SEGMENTATION | DX_RENDER_NO_CULL)) return fail(DX_EINVAL, "cameras: unknown flag");
+  if (!(flags & (DX_RENDER_DEPTH | DX_RENDER_SEGMENTATION)))
+    return fail(DX_EINVAL, "cameras: no output flag (DX_RENDER_DEPTH / DX_RENDER_SEGMENTATION)");
+  if (ncam > DX_RENDER_MAX_CAMERAS) return fail(DX_ELIMIT, "cameras: more than 8 cameras");
+  if (width > DX_RENDER_MAX_SIDE || height > DX_RENDER_MAX_SIDE) return fail(DX_ELIMIT, "cameras: a side above 512 pixels");
+  const unsigned long long npix = (unsigned long long)b->nenv * ncam * height * width;
+  if (npix >= 0x80000000ull) return fail(DX_ELIMIT, "cameras: nenv * ncam * height * width reaches 2^31");
+  RenderArgs A{};
+  for (int i = 0; i < ncam; i++) {
+    const dx_camera& c = cams[i];
+    if (!(c.fovy > 0.f && c.fovy < 180.f)) return fail(DX_EINVAL, "cameras: fovy outside (0, 180) degrees");
+    if (!(c.near_ > 0.f) || !(c.far_ > c.near_) || !std::isfinite(c.far_))
+      return fail(DX_EINVAL, "cameras: need 0 < near < far (finite)");
+    if (c.body < -1 || c.body >= b->dm.nbody) return fail(DX_EINVAL, "cameras: body outside [-1, nbody)");
+    for (int k = 0; k < 3; k++)
+      if (!std::isfinite(c.pos[k])) return fail(DX_EINVAL, "cameras: a non-finite position");
+    if (!camera_frame(c, A.cam[i], height)) return fail(DX_EINVAL, "cameras: degenerate xyaxes");
+  }
+  if (int rc = render_base(b, A)) return rc;
+  void *nd = b->rnd_depth, *ns = b->rnd_seg;
+  bool fd = false, fs = false;
+  if (flags & DX_RENDER_DEPTH)
+    if (int rc = render_buffer(b, b->rnd_depth, b->rnd_depth_cap, (size_t)npix, &nd, &fd)) return rc;
+  if (flags & DX_RENDER_SEGMENTATION)
+    if (int rc = render_buffer(b, b->rnd_seg, b->rnd_seg_cap, (size_t)npix, &ns, &fs)) {
+      if (fd) (void)hipFree(nd);
+      return rc;
+    }
+  if (hipStreamSynchronize(b->stream) != hipSuccess) {
+    if (fd) (void)hipFree(nd);
+    if (fs) (void)hipFree(ns);
+    return fail(DX_EHIP, "cameras: stream sync failed");
+  }
+  // every step has succeeded: the new buffers replace the old ones
+  if (fd) render_adopt(b, (void**)&b->rnd_depth, &b->rnd_depth_cap, nd, (size_t)npix);
+  if (fs) render_adopt(b, (void**)&b->rnd_seg, &b->rnd_seg_cap, ns, (size_t)npix);
+  A.ncam = ncam; A.W = width; A.H = height;
+  A.tiles_x = (width + DX_RENDER_TILE - 1) / DX_RENDER_TILE;
+  A.tiles_y = (height + DX_RENDER_TILE - 1) / DX_RENDER_TILE;
+  A.no_cull = (flags & DX_RENDER_NO_CULL) ? 1 : 0;
+  A.depth = (flags & DX_RENDER_DEPTH) ? b->rnd_depth : nullptr;
+  A.seg = (flags & DX_RENDER_SEGMENTATION) ? b->rnd_seg : nullptr;
+  b->RA = A;
+  b->rnd_flags = flags;
+  if (b->rnd_prev_bodies < 0) b->rnd_prev_bodies = b->db.out_bodies;
+  b->db.out_bodies = 1;
+  return 0;
+}
+
+extern "C" int dx_render(dx_batch* b) {
+  if (!b) return fail(DX_EINVAL, "null batch");
+  if (!b->RA.ncam) return fail(DX_EINVAL, "render: no cameras (dx_render_set_cameras)");
+  HIPCHK(hipSetDevice(b->device));
+  RenderArgs A = b->RA;
+  A.stats = b->rnd_stats_on ? b->rnd_stats : nullptr;
+  HIPCHK(dx_launch_render(b->stream, A));
+  return 0;
+}
+
+extern "C" int dx_render_output(dx_batch* b, int which, void** devptr) {
+  if (!b || !devptr) return fail(DX_EINVAL, "null argument");
+  if (!b->RA.ncam) return fail(DX_EINVAL, "render: no cameras (dx_render_set_cameras)");
+  if (which == DX_RENDER_DEPTH && b->RA.depth) { *devptr = b->RA.depth; return 0; }
+  if (which == DX_RENDER_SEGMENTATION && b->RA.seg) { *devptr = b->RA.seg; return 0; }
+  return fail(DX_EINVAL, "render: that output is not enabled");
+}
+
+extern "C" int dx_render_get(dx_batch* b, int which, void* dst_host, int32_t env0, int32_t n) {
+  void* src = nullptr;
+  if (int rc = dx_render_output(b, which, &src)) return rc;
+  if (!dst_host || env0 < 0 || n < 0 || env0 + n > b->nenv) return fail(DX_EINVAL, "render: bad env range or null destination");
+  HIPCHK(hipSetDevice(b->device));
+  const size_t per = (size_t)b->RA.ncam * b->RA.H * b->RA.W * 4;
+  HIPCHK(hipMemcpyAsync(dst_host, (const char*)src + per * env0, per * n, hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+extern "C" int dx_render_stats(dx_batch* b, int enable, uint64_t out[3]) {
+  if (!b) return fail(DX_EINVAL, "null batch");
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  if (!b->rnd_stats)
+    if (int rc = balloc(b, (void**)&b->rnd_stats, 3 * 8)) return rc;
+  HIPCHK(hipStreamSynchronize(b->stream));
+  if (out) HIPCHK(hipMemcpy(out, b->rnd_stats, 3 * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemset(b->rnd_stats, 0, 3 * 8));
+  b->rnd_stats_on = enable != 0;
+  return 0;
+}
+
+extern "C" int dx_ray(dx_batch* b, const float* origin, const float* dir, int32_t nray, float* dist, int32_t* geom) {
+  if (!b) return fail(DX_EINVAL, "null batch");
+  if (!origin || !dir || !dist || !geom) return fail(DX_EINVAL, "ray: null origin, dir, dist or geom");
+  if (nray < 1) return fail(DX_EINVAL, "ray: nray must be positive");
+  if ((unsigned long long)b->nenv * nray >= 0x80000000ull / 4) return fail(DX_ELIMIT, "ray: nenv * nray reaches 2^29");
+  HIPCHK(hipSetDevice(b->device));
+  RenderArgs A{};
+  if (int rc = render_base(b, A)) return rc;
+  const size_t E = b->nenv;
+  std::unique_ptr<CallScratch> S;  // (synchronises the stream when it goes)
+  DlsArg ao, ad, at, ag;
+  if (!dls_arg(ao, origin, E * nray * 12, S, b->stream) || !dls_arg(ad, dir, E * nray * 12, S, b->stream) ||
+      !dls_arg(at, dist, E * nray * 4, S, b->stream) || !dls_arg(ag, geom, E * nray * 4, S, b->stream))
+    return fail(DX_ENOMEM, "device scratch allocation failed");
+  if (ao.staged) HIPCHK(hipMemcpyAsync(ao.dev, ao.user, ao.bytes, hipMemcpyHostToDevice, b->stream));
+  if (ad.staged) HIPCHK(hipMemcpyAsync(ad.dev, ad.user, ad.bytes, hipMemcpyHostToDevice, b->stream));
+  A.nray = nray;
+  A.ray_o = (const float*)ao.dev;
+  A.ray_d = (const float*)ad.dev;
+  A.ray_dist = (float*)at.dev;
+  A.ray_geom = (int*)ag.dev;
+  HIPCHK(dx_launch_rays(b->stream, A));
+  if (at.staged) HIPCHK(hipMemcpyAsync(at.user, at.dev, at.bytes, hipMemcpyDeviceToHost, b->stream));
+  if (ag.staged) HIPCHK(hipMemcpyAsync(ag.user, ag.dev, ag.bytes, hipMemcpyDeviceToHost, b->stream));
+  if (S) HIPCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
 extern "C" void* dx_stream(dx_batch* b) { return b ? (void*)b->stream : nullptr; }
 
 extern "C" int dx_sync(dx_batch* b) {
@@ -1791,6 +2141,13 @@ extern "C" int dx_sync(dx_batch* b) {
 
 extern "C" int dx_set_outputs(dx_batch* b, int bodies) {
   if (!b) return fail(DX_EINVAL, "null batch");
+  if (b->RA.ncam) {
+    // cameras read the body poses: they stay on, and the request is what comes back when
+    // the cameras go off
+    b->rnd_prev_bodies = bodies != 0;
+    b->db.out_bodies = 1;
+    return 0;
+  }
   b->db.out_bodies = bodies != 0;
   return 0;
 }
@@ -2200,6 +2557,10 @@ static int env_observe(dx_env* e) {
   if (e->cf_on)
     if (int rc = launch_sensor(e->batch, &e->CF, e->cf_out)) return rc;
   if (int rc = env_hand_obs(e)) return rc;
+  // the cameras (dx_render.hip) over the body poses the same observation pass wrote: an env
+  // that returned FIRST shows its reset state
+  if (e->batch->RA.ncam)
+    if (int rc = dx_render(e->batch)) return rc;
   if (!e->O.on) return 0;
   HIPCHK(dx_launch_obs_pipe(e->batch->stream, e->O, 0));
   return 0;
@@ -2216,7 +2577,7 @@ static int env_observe(dx_env* e) {
 static int env_run(dx_env* e, const float* action, bool random = false, uint64_t seed = 0, int step = 0) {
   dx_batch* b = e->batch;
   HIPCHK(hipSetDevice(b->device));
-  if (e->H.mask & HOBS_NEEDS_BODIES) b->db.out_bodies = 1;  // (whatever dx_set_outputs was told since)
+  if ((e->H.mask & HOBS_NEEDS_BODIES) || b->RA.ncam) b->db.out_bodies = 1;  // (whatever dx_set_outputs was told since)
   if (e->PT.nb && (action || random)) {
     // the random pushes: one launch ahead of the step's, which then read the env's own xfrc
     // rows (per-env mode again, from the current shared array, had dx_set_xfrc left it)
@@ -2604,6 +2965,25 @@ extern "C" int dx_env_set_hand_observables(dx_env* e, const dx_hand_obs* cfg) {
   return 0;
 }
 
+// The cameras of the env's batch.  The batch of a dx_env steps without body poses by default:
+// they are refreshed for the current state first, so the images the call leaves describe it.
+extern "C" int dx_env_set_cameras(dx_env* e, const dx_camera* cams, int32_t ncam, int32_t width, int32_t height,
+                                  int32_t flags) {
+  if (!e) return fail(DX_EINVAL, "null env");
+  dx_batch* b = e->batch;
+  const int bodies = b->db.out_bodies;
+  if (int rc = dx_render_set_cameras(b, cams, ncam, width, height, flags)) return rc;
+  if (!ncam) {
+    if (e->H.mask & HOBS_NEEDS_BODIES) b->db.out_bodies = 1;  // the hand observables still read them
+    return 0;
+  }
+  if (!bodies)
+    if (int rc = env_refresh_body_poses(e)) return rc;
+  if (int rc = dx_render(b)) return rc;
+  HIPCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
 extern "C" int dx_env_hand_obs_dim(const dx_env* e) {
   if (!e) return fail(DX_EINVAL, "null env");
   return e->H.mask ? e->H.dim : 0;
@@ -2937,6 +3317,16 @@ extern "C" int dx_env_output(dx_env* e, int which, void** devptr) {
     case DX_OUT_PERTURB:
       if (!e->PT.nb) return fail(DX_EINVAL, "no pushes: dx_env_set_perturbation has not enabled them");
       *devptr = e->PT.wrench;
+      return 0;
+    case DX_OUT_DEPTH:
+      if (!e->batch->RA.ncam || !e->batch->RA.depth)
+        return fail(DX_EINVAL, "no depth images: dx_env_set_cameras has no camera with DX_RENDER_DEPTH on");
+      *devptr = e->batch->RA.depth;
+      return 0;
+    case DX_OUT_SEGMENTATION:
+      if (!e->batch->RA.ncam || !e->batch->RA.seg)
+        return fail(DX_EINVAL, "no segmentation images: dx_env_set_cameras has no camera with DX_RENDER_SEGMENTATION on");
+      *devptr = e->batch->RA.seg;
       return 0;
   }
   return fail(DX_EINVAL, "unknown output");

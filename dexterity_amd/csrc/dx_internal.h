@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/dx.h"
+
 #define DX_WAVE 64
 // Contact pool, two tiers.  The step kernel keeps DX_NCON_MAX = 32 contacts per env and
 // physics step in LDS; a physics step that finds more is not truncated but deferred, from
@@ -565,6 +567,43 @@ hipError_t dx_launch_hand_obs(hipStream_t stream, const HandObs& H);
 // (restart: every env starts its history afresh from its current row), and its test hook
 hipError_t dx_launch_obs_pipe(hipStream_t stream, const ObsPipe& O, int restart);
 hipError_t dx_launch_obs_noise_draw(hipStream_t stream, int nenv, int n, uint32_t* mt, double* out);
+
+// dx_render.hip: depth / segmentation cameras and batched rays, a ray cast against the
+// compiled geoms (dx_render_set_cameras, dx_render, dx_ray), queued behind the step's
+// launches.  The step kernels know nothing of it: it reads DX_XPOS / DX_XQUAT and the
+// model's geom tables.
+#define DX_RENDER_TILE 16     // a workgroup renders one 16 x 16 pixel tile of one (env, camera)
+#define DX_RENDER_THREADS 256 // four waves, each an 8 x 8 block of the tile
+#define DX_RENDER_CHUNK 256   // geoms culled per pass (one per lane), the LDS list's capacity
+#define DX_RENDER_REC 24      // words per list record (dx_render.hip)
+struct RenderCam {
+  float pos[3];               // in the frame of `body` (world when body < 0)
+  float x[3], y[3], z[3];     // the orthonormal camera frame (looks along -z), same frame
+  float f;                    // focal length in pixels, 0.5 H / tan(fovy / 2)
+  float near_, far_;
+  int body;
+};
+struct RenderArgs {
+  int nenv, ngeom, nbody;
+  int ncam, W, H, tiles_x, tiles_y;
+  int no_cull;
+  RenderCam cam[DX_RENDER_MAX_CAMERAS];  // (include/dx.h)
+  const float *xpos, *xquat;                       // the batch's
+  const DXG int *geom_type, *geom_bodyid, *geom_dataid;
+  const DXG float *geom_size, *geom_pos, *geom_mat, *geom_bsphere;
+  const DXG int *mesh_planeadr, *mesh_planenum;    // a hull's run in plane4
+  const DXG float4* plane4;                        // (n, d), n x + d <= 0 inside, geom frame
+  float* depth;                                    // [nenv][ncam][H][W], or null
+  int* seg;                                        // [nenv][ncam][H][W], or null
+  unsigned long long* stats;                       // [0] survivors summed, [1] their max, [2] tiles; or null
+  // rays (dx_ray): [nenv][nray][3] origins and directions, [nenv][nray] outputs
+  int nray;
+  const float *ray_o, *ray_d;
+  float* ray_dist;
+  int* ray_geom;
+};
+hipError_t dx_launch_render(hipStream_t stream, const RenderArgs& A);
+hipError_t dx_launch_rays(hipStream_t stream, const RenderArgs& A);
 
 // dx_perturb.hip: the random pushes, queued ahead of the step's launches, and their test hook
 hipError_t dx_launch_perturb(hipStream_t stream, const Perturb& P);

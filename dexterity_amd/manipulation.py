@@ -28,6 +28,7 @@ from typing import Dict, Optional
 import numpy as np
 
 from dexterity_amd import _lib
+from dexterity_amd import cameras as cameras_lib
 from dexterity_amd import effectors as effectors_lib
 from dexterity_amd import hands as hands_lib
 from dexterity_amd import physics as physics_lib
@@ -555,6 +556,8 @@ class GoalEnvironment:
         self.contact_force_pads = 0
         # configure_perturbations' current settings (None: the random pushes are off)
         self.perturbation_options = None
+        # enable_cameras' current settings (None: the cameras are off)
+        self.camera_options = None
         if np.isfinite(self.time_limit):
             _lib.check(L.dx_env_set_time_limit(self.ptr, self.time_limit))
         # max_time_per_goal in fp64 (the params carry it as a float)
@@ -599,6 +602,14 @@ class GoalEnvironment:
         if self.contact_force_pads:  # (never buffered: the observation pipeline's row does not carry them)
             lead = () if self.strip_singleton_obs_buffer_dim else (1,)
             spec[CONTACT_FORCES_KEY] = Array(lead + (self.contact_force_pads, 3), np.float64, name=CONTACT_FORCES_KEY)
+        if self.camera_options:  # (never buffered either)
+            o = self.camera_options
+            for name in o["names"]:
+                if o["depth"]:
+                    spec[f"{name}_depth"] = Array((o["height"], o["width"], 1), np.float32, name=f"{name}_depth")
+                if o["segmentation"]:
+                    spec[f"{name}_segmentation"] = Array((o["height"], o["width"], 2), np.int32,
+                                                         name=f"{name}_segmentation")
         return spec
 
     # ---------------------------------------------------------------- stepping
@@ -649,6 +660,7 @@ class GoalEnvironment:
         elif self.hand_obs_dim:  # the packed row does not carry them: one more copy
             ts.observation.update(self._hand_observation())
         ts.observation.update(self._contact_observation())
+        ts.observation.update(self._camera_observation())
         return ts
 
     def _timestep_packed(self, packed: np.ndarray) -> TimeStep:
@@ -795,6 +807,69 @@ class GoalEnvironment:
             raise _lib.DxError("contact forces are off (enable_contact_forces)")
         n = self.contact_force_pads
         return self._read(_lib.OUT_CONTACT_FORCE, np.float32, 3 * n).reshape(self.num_envs, n, 3)
+
+    # ---------------------------------------------------------------- cameras
+    def enable_cameras(self, configs_or_names, height: int = 84, width: int = 84, depth: bool = True,
+                       segmentation: bool = False, near: float = 0.01, far: float = 10.0) -> None:
+        """The reference's camera observables (manipulation/shared/cameras.py:53-64 at the
+        84 x 84 spec of observations.py:62-74) as depth and segmentation images, ray cast on
+        the device behind every control step (include/dx.h dx_env_set_cameras).  Cameras are
+        `dexterity_amd.cameras.CameraConfig`s or names of its five (`front_close`, ...); an
+        empty list switches the feature off.  Per camera, after the existing keys of
+        `observation_spec()` and of every TimeStep:
+          f"{name}_depth"         [B, H, W, 1] float32, metres along the optical axis, `far`
+                                  where nothing is seen (dm_control's depth=True);
+          f"{name}_segmentation"  [B, H, W, 2] int32, (geom id, 5 = mjOBJ_GEOM), or (-1, -1)
+                                  where nothing is seen (dm_control's segmentation=True).
+        They describe the same state as the rest of the observation, also for an env that
+        returned FIRST, and right after this call.  Only the compiled (collision) geoms
+        exist; there is no RGB.  The packed rows, the observation pipeline and the
+        checkpoint do not carry the images.  Bad options raise ValueError."""
+        cfgs = cameras_lib.resolve(configs_or_names)
+        if not cfgs:
+            _lib.check(_lib.load().dx_env_set_cameras(self.ptr, None, 0, 0, 0, 0))
+            self.camera_options = None
+            return
+        bodies = cameras_lib.validate(cfgs, width, height, depth, segmentation, near, far, self.num_envs,
+                                      self.task.compiled.names["body"])
+        arr = (_lib.Camera * len(cfgs))()
+        for c, cfg, body in zip(arr, cfgs, bodies):
+            c.pos[:] = [float(v) for v in cfg.pos]
+            c.xyaxes[:] = [float(v) for v in cfg.xyaxes]
+            c.fovy, c.near_, c.far_, c.body = float(cfg.fovy), float(near), float(far), body
+        flags = (_lib.RENDER_DEPTH if depth else 0) | (_lib.RENDER_SEGMENTATION if segmentation else 0)
+        _lib.check(_lib.load().dx_env_set_cameras(self.ptr, arr, len(cfgs), int(width), int(height), flags))
+        self.camera_options = dict(names=tuple(c.name for c in cfgs), configs=tuple(cfgs), height=int(height),
+                                   width=int(width), depth=bool(depth), segmentation=bool(segmentation),
+                                   near=float(near), far=float(far))
+
+    def depth_ptr(self) -> int:
+        """Device address of the [num_envs, ncam, H, W] float32 depth images (while enabled)."""
+        return self._out(_lib.OUT_DEPTH)
+
+    def segmentation_ptr(self) -> int:
+        """Device address of the [num_envs, ncam, H, W] int32 geom ids (while enabled)."""
+        return self._out(_lib.OUT_SEGMENTATION)
+
+    def _camera_observation(self) -> "collections.OrderedDict[str, np.ndarray]":
+        """The cameras' images while enable_cameras is on (one device-to-host copy per
+        enabled output); empty, and no copy, while it is off."""
+        out = collections.OrderedDict()
+        o = self.camera_options
+        if not o:
+            return out
+        n = len(o["names"]) * o["height"] * o["width"]
+        shape = (self.num_envs, len(o["names"]), o["height"], o["width"])
+        dep = self._read(_lib.OUT_DEPTH, np.float32, n).reshape(shape) if o["depth"] else None
+        seg = self._read(_lib.OUT_SEGMENTATION, np.int32, n).reshape(shape) if o["segmentation"] else None
+        for k, name in enumerate(o["names"]):
+            if dep is not None:
+                out[f"{name}_depth"] = dep[:, k, :, :, None].copy()
+            if seg is not None:
+                s = seg[:, k]
+                out[f"{name}_segmentation"] = np.stack([s, np.where(s >= 0, cameras_lib.OBJ_GEOM, -1)],
+                                                       axis=-1).astype(np.int32)
+        return out
 
     # ---------------------------------------------------------------- random pushes
     def configure_perturbations(self, bodies=("prop",), probability: float = 0.0, force_range=(0.0, 0.0),
@@ -1016,6 +1091,7 @@ class GoalEnvironment:
         else:
             observation.update(self._hand_observation())
         observation.update(self._contact_observation())
+        observation.update(self._camera_observation())
         return TimeStep(st.astype(np.int32), rew, disc, observation)
 
     def goals(self) -> np.ndarray:
@@ -1092,13 +1168,15 @@ def load(domain_name: str, task_name: str, seed: Optional[int] = None,
          strip_singleton_obs_buffer_dim: bool = True, time_limit: Optional[float] = None,
          num_envs: int = 1, device: int = 0, env_offset: int = 0, noise_scale: Optional[float] = None,
          noise_seed: Optional[int] = None, smooth_alpha: Optional[float] = None,
-         previous_action: bool = False) -> GoalEnvironment:
+         previous_action: bool = False, cameras=None, camera_options: Optional[dict] = None) -> GoalEnvironment:
     """manipulation/__init__.py:56-86, batched: the reference's arguments in its order,
     then the batch size and the GPU.  `time_limit=None` keeps the task's own limit
     (inf for every suite task).  Env e of the batch is the reference's environment
     loaded with seed `seed + env_offset + e`; `env_offset` places a shard of a sharded
     job (distributed.env_shard) in the job's env numbering.  The last four arguments are
-    `GoalEnvironment.configure_actions`' (default: the action pipeline off)."""
+    `GoalEnvironment.configure_actions`' (default: the action pipeline off).  `cameras`
+    (CameraConfigs or names) and `camera_options` (height, width, depth, segmentation, near,
+    far) are `GoalEnvironment.enable_cameras`' (default: no cameras)."""
     key = (domain_name, task_name)
     if domain_name not in {d for d, _ in SUITE}:
         raise ValueError(f"Unknown domain: {domain_name}")
@@ -1109,6 +1187,8 @@ def load(domain_name: str, task_name: str, seed: Optional[int] = None,
     if noise_scale is not None or smooth_alpha is not None or previous_action:
         env.configure_actions(noise_scale=noise_scale, noise_seed=noise_seed, smooth_alpha=smooth_alpha,
                               previous_action=previous_action)
+    if cameras:
+        env.enable_cameras(cameras, **(camera_options or {}))
     return env
 
 

@@ -16,6 +16,7 @@ import numpy as np
 
 from dexterity_amd import _lib
 from dexterity_amd import blob as blob_lib
+from dexterity_amd import cameras as cameras_lib
 from dexterity_amd.mjcf.compiler import CompiledModel
 
 
@@ -41,6 +42,15 @@ class Model:
 
     def width(self, field: int) -> int:
         return _lib.check(_lib.load().dx_field_width(self.ptr, field))
+
+    def hull_planes(self, mesh: int) -> np.ndarray:
+        """[n, 4] float32 face planes (unit n, d; n.x + d <= 0 inside, geom frame) the library
+        derives for hull `mesh` (include/dx.h dx_model_hull_planes; no GPU needed)."""
+        L = _lib.load()
+        n = _lib.check(L.dx_model_hull_planes(self.ptr, int(mesh), None, 0))
+        out = np.zeros((n, 4), np.float32)
+        _lib.check(L.dx_model_hull_planes(self.ptr, int(mesh), out.ctypes.data, n))
+        return out
 
     def __del__(self):
         if getattr(self, "ptr", None) and _lib._lib is not None:
@@ -220,6 +230,80 @@ class BatchedPhysics:
         if npad:
             _lib.check(_lib.load().dx_get_field(self.ptr, _lib.PAD_FORCE, out.ctypes.data, 0, self.nenv))
         return out
+
+    # ------------------------------------------------------------------ #
+    # depth / segmentation cameras and batched rays (include/dx.h dx_render_set_cameras)
+    def set_cameras(self, configs, width: int, height: int, depth: bool = True, segmentation: bool = False,
+                    near: float = 0.01, far: float = 10.0, cull: bool = True) -> None:
+        """The cameras `render()` casts: CameraConfigs or names of the five of
+        `dexterity_amd.cameras` (an empty list switches them off).  Depth is the distance
+        along the optical axis in metres, `far` on a miss; segmentation the geom id, -1 on a
+        miss.  `cull=False` renders without the per-tile geom cull (the same images).  Bad
+        options raise ValueError before any library call."""
+        cfgs = cameras_lib.resolve(configs)
+        L = _lib.load()
+        if not cfgs:
+            _lib.check(L.dx_render_set_cameras(self.ptr, None, 0, 0, 0, 0))
+            self._cameras = ()
+            return
+        bodies = cameras_lib.validate(cfgs, width, height, depth, segmentation, near, far, self.nenv,
+                                      self.model.compiled.names["body"])
+        arr = (_lib.Camera * len(cfgs))()
+        for c, cfg, body in zip(arr, cfgs, bodies):
+            c.pos[:] = [float(v) for v in cfg.pos]
+            c.xyaxes[:] = [float(v) for v in cfg.xyaxes]
+            c.fovy, c.near_, c.far_, c.body = float(cfg.fovy), float(near), float(far), body
+        flags = (_lib.RENDER_DEPTH if depth else 0) | (_lib.RENDER_SEGMENTATION if segmentation else 0) | \
+            (0 if cull else _lib.RENDER_NO_CULL)
+        _lib.check(L.dx_render_set_cameras(self.ptr, arr, len(cfgs), int(width), int(height), flags))
+        self._cameras = tuple(cfgs)
+        self._camera_shape = (self.nenv, len(cfgs), int(height), int(width))
+
+    def render(self) -> None:
+        """Renders the current poses (after `step()` or `forward()`) on the batch's stream."""
+        _lib.check(_lib.load().dx_render(self.ptr))
+
+    def _image(self, which: int, dtype) -> np.ndarray:
+        if not getattr(self, "_cameras", ()):
+            raise _lib.DxError("no cameras (set_cameras)")
+        out = np.empty(self._camera_shape, dtype=dtype)
+        _lib.check(_lib.load().dx_render_get(self.ptr, which, out.ctypes.data, 0, self.nenv))
+        return out
+
+    def depth(self) -> np.ndarray:
+        """[B, ncam, H, W] float32 host copy of the last render's depth images."""
+        return self._image(_lib.RENDER_DEPTH, np.float32)
+
+    def segmentation(self) -> np.ndarray:
+        """[B, ncam, H, W] int32 host copy of the last render's geom ids (-1: none)."""
+        return self._image(_lib.RENDER_SEGMENTATION, np.int32)
+
+    def image_ptr(self, which: int) -> int:
+        """Device address of the depth (`_lib.RENDER_DEPTH`) or segmentation images."""
+        p = ctypes.c_void_p()
+        _lib.check(_lib.load().dx_render_output(self.ptr, which, ctypes.byref(p)))
+        return p.value
+
+    def render_stats(self, enable: bool = True):
+        """(survivors summed, their maximum, tiles) of the renders since the last call: the
+        geoms per pixel tile that survive the cull.  `enable` switches the counting."""
+        out = (ctypes.c_uint64 * 3)()
+        _lib.check(_lib.load().dx_render_stats(self.ptr, int(enable), out))
+        return tuple(int(v) for v in out)
+
+    def ray(self, origins, dirs):
+        """A batched mj_ray at the current poses: origins / dirs [B, nray, 3] (world frame;
+        dirs need not be normalised) -> (dist [B, nray] float32 along the normalised dir,
+        geom [B, nray] int32); a miss is -1 / -1."""
+        o = np.ascontiguousarray(origins, dtype=np.float32)
+        d = np.ascontiguousarray(dirs, dtype=np.float32)
+        if o.ndim != 3 or o.shape[0] != self.nenv or o.shape[2] != 3 or d.shape != o.shape or o.shape[1] < 1:
+            raise ValueError(f"origins and dirs must both be [{self.nenv}, nray, 3], got {o.shape} and {d.shape}")
+        dist = np.empty(o.shape[:2], np.float32)
+        geom = np.empty(o.shape[:2], np.int32)
+        _lib.check(_lib.load().dx_ray(self.ptr, o.ctypes.data, d.ctypes.data, o.shape[1], dist.ctypes.data,
+                                      geom.ctypes.data))
+        return dist, geom
 
     def debug(self, enable: bool = True) -> None:
         _lib.check(_lib.load().dx_debug_enable(self.ptr, int(enable)))

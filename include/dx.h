@@ -294,7 +294,12 @@ enum dx_env_out { DX_OUT_OBS = 0, DX_OUT_REWARD = 1, DX_OUT_DISCOUNT = 2, DX_OUT
                                                pads; while they are on (below) */,
                   DX_OUT_PERTURB = 12 /* [nenv][nb][6] f32, the random pushes' wrenches (force,
                                          torque) on the nb configured bodies; while they are on
-                                         (below) */ };
+                                         (below) */,
+                  DX_OUT_DEPTH = 13 /* [nenv][ncam][H][W] f32, the cameras' depth images; while
+                                       cameras with DX_RENDER_DEPTH are on (dx_env_set_cameras) */,
+                  DX_OUT_SEGMENTATION = 14 /* [nenv][ncam][H][W] int32, the geom id each pixel sees
+                                              (-1: none); while cameras with DX_RENDER_SEGMENTATION
+                                              are on */ };
 dx_env* dx_env_create(const dx_model* m, int32_t nenv, int32_t device, int32_t task, uint64_t seed,
                       const float* params, int32_t nparams);
 /* One shard of a job's environments: this handle's env e is the job's env env0 + e.
@@ -691,6 +696,98 @@ int dx_jac_object(dx_batch* b, const int32_t* types, const int32_t* ids, int32_t
  * regularization is DX_EINVAL.  The batch's state is not modified. */
 int dx_dls_map(dx_batch* b, const int32_t* types, const int32_t* ids, int32_t nobj,
                float regularization, const float* target_vel, float* qvel_out, int32_t* status);
+
+/* Depth and segmentation cameras, batched rays -------------------------- */
+/* The reference's vision observables (manipulation/shared/observations.py:62-111, the 84 x 84
+ * camera spec with its `depth` and `segmentation` switches; cameras.py:22-50) as a ray cast
+ * against the geoms the compiled model holds -- the plane, boxes, spheres, capsules and
+ * convex hulls -- in one launch behind the step (dx_render.hip).  Shaded RGB is not built.
+ *
+ * Camera model ([3P] MuJoCo's pinhole).  The frame comes from xyaxes: x normalised, y made
+ * orthogonal to x and normalised, z = x (x) y; the camera looks along -z.  fovy is the
+ * vertical field of view in degrees.  Pixel (r, c), row 0 on top, has its centre at
+ * (c + 0.5, r + 0.5); with f = 0.5 H / tan(fovy / 2) its ray is
+ *   x (c + 0.5 - W/2) / f - y (r + 0.5 - H/2) / f - z,
+ * not normalised, so the ray parameter of a hit is the depth along the optical axis in
+ * metres (what dm_control's depth=True returns).  body = -1: pos / xyaxes are in the world;
+ * body >= 0: in that body's frame, the camera rigidly attached (a palm camera).
+ *
+ * A pixel sees the nearest geom whose ENTRY depth lies in [near_, far_].  A hull is clipped
+ * against its face planes, a box against its slabs, spheres and capsules in closed form; the
+ * plane is infinite and one-sided (seen only from the side its normal faces).  Misses write
+ * far_ to the depth and -1 to the segmentation; hits write the compiled model's geom id.
+ * Stated deviations from an OpenGL render: a geom the near plane cuts (the camera inside
+ * it, or its entry nearer than near_) is not seen at all, rather than showing its inside;
+ * only compiled geoms exist -- the collision geoms, not the visual meshes and not the
+ * reorient task's hint cube; and a hull is seen along a ray only where its chord is longer
+ * than 8 ulp of the depth (about 5e-7 m at half a metre): the Shadow hand's meshes hold flat
+ * pieces 6e-8 m thick, which fp32 would otherwise see or miss by rounding.  Such a piece is
+ * therefore invisible also when it faces the camera: the pixel shows what lies behind it.
+ *
+ * Hull face planes are derived by the library on the host when cameras or rays are first
+ * used (the assets carry vertices and adjacency, no faces): the plane through a vertex and
+ * two neighbours that are neighbours of each other is a face when every vertex lies on one
+ * side of it (tolerance 1e-9 max|v|); coplanar triangles are merged.  dx_model_hull_planes
+ * (test hook, like dx_hull_support) copies the first min(n, count) planes of hull `mesh` to
+ * out as (nx, ny, nz, d), unit n, n.x + d <= 0 inside, geom frame, and returns the count.
+ *
+ * dx_render_set_cameras: flags selects the outputs (at least one of DX_RENDER_DEPTH,
+ * DX_RENDER_SEGMENTATION); DX_RENDER_NO_CULL renders without the per-tile geom cull and
+ * gives bit-identical images (a test and measurement switch).  ncam = 0 switches the
+ * feature off and frees nothing a later call would need.  While cameras are on the batch
+ * writes body poses (dx_set_outputs(batch, 1); the earlier setting is restored when they
+ * go off, and a dx_set_outputs call made while they are on does not switch the poses off:
+ * it sets what is restored); on a batch that was stepping without them the poses are those
+ * of the next dx_step / dx_forward.  It synchronises the stream.  DX_EINVAL (configuration unchanged):
+ * a degenerate xyaxes, fovy outside (0, 180), near_ <= 0 or far_ <= near_, a body outside
+ * [-1, nbody), no output flag; DX_ELIMIT: more than 8 cameras, a side above 512, or
+ * nenv * ncam * height * width >= 2^31.
+ * dx_render renders the batch's current poses (after dx_step or dx_forward) on its stream.
+ * dx_render_output gives the device address of [nenv][ncam][height][width] f32
+ * (which = DX_RENDER_DEPTH) or int32 (DX_RENDER_SEGMENTATION); dx_render_get copies envs
+ * env0 .. env0+n-1 of one to host memory and synchronises.
+ * Exact contracts: a pixel's value does not depend on the tile it falls in, on the other
+ * cameras or on the cull; two renders of one state are bit-identical.
+ * dx_render_stats (measurement): enable != 0 makes later renders count, per pixel tile,
+ * the geoms that survive the cull; out (may be null) = {survivors summed, their maximum,
+ * tiles} since the last call, which also clears them.  It synchronises the stream.
+ *
+ * dx_ray: nray rays per env, origin / dir [nenv][nray][3], dist [nenv][nray] f32, geom
+ * [nenv][nray] int32, each in host or device memory as dx_dls_map accepts them.  dir is
+ * normalised by the library and dist is along it: the nearest geom ENTERED at dist >= 0, a
+ * miss gives -1 and geom -1 ([3P] mj_ray's return convention).  Unlike mj_ray, which can
+ * report the far side of a geom the ray starts inside, a ray here never sees a geom it
+ * starts inside; the camera rules above (one-sided plane, thin hulls) hold too.  It reads the poses the last dx_step / dx_forward wrote (body poses
+ * must be on, the default of a dx_batch). */
+typedef struct dx_camera {
+  float pos[3];
+  float xyaxes[6];
+  float fovy;            /* degrees */
+  float near_, far_;     /* metres along the optical axis */
+  int32_t body;          /* -1: world-fixed */
+} dx_camera;
+enum { DX_RENDER_DEPTH = 1, DX_RENDER_SEGMENTATION = 2, DX_RENDER_NO_CULL = 4 };
+#define DX_RENDER_MAX_CAMERAS 8
+#define DX_RENDER_MAX_SIDE 512
+int dx_model_hull_planes(const dx_model* m, int32_t mesh, float* out /* [n][4] or NULL */, int32_t n);
+int dx_render_set_cameras(dx_batch* b, const dx_camera* cams, int32_t ncam, int32_t width, int32_t height,
+                          int32_t flags);
+int dx_render(dx_batch* b);
+int dx_render_output(dx_batch* b, int which, void** devptr);
+int dx_render_get(dx_batch* b, int which, void* dst_host, int32_t env0, int32_t n);
+int dx_render_stats(dx_batch* b, int enable, uint64_t out[3]);
+int dx_ray(dx_batch* b, const float* origin, const float* dir, int32_t nray, float* dist, int32_t* geom);
+/* Env level: the cameras of a dx_env's batch, rendered behind every call that produces the
+ * observation (dx_env_reset, dx_env_step, dx_env_step_random, dx_env_step_host), after its
+ * last launch: DX_OUT_DEPTH / DX_OUT_SEGMENTATION describe the same state as DX_OUT_OBS, and an
+ * env that returned FIRST shows its reset state.  dx_env_set_cameras may be called between
+ * steps and leaves the images holding the current state; ncam = 0 switches them off (the
+ * default: a control step then launches what it launched before, and dx_env_output of the two
+ * fails).  The images are not part of the packed row, dx_env_step_host's row, the all-gather,
+ * the observation pipeline or the checkpoint: after dx_env_load they are stale until the next
+ * step or reset. */
+int dx_env_set_cameras(dx_env* e, const dx_camera* cams, int32_t ncam, int32_t width, int32_t height,
+                       int32_t flags);
 
 /* Timing ---------------------------------------------------------------- */
 /* When enabled, HIP events bracket the step-kernel launches on the batch stream -- every
