@@ -21,19 +21,23 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libdx.so")
 SPECS = os.path.join(CSRC, "dx_specs.inc")
-SOURCES = ("dx_step.hip", "dx_ik.hip", "dx_dls.hip", "dx_task.hip", "dx_sensor.hip", "dx_observe.hip", "dx_obspipe.hip",
-           "dx_perturb.hip", "dx_render.hip", "dx_api.hip")
-HEADERS = ("dx_internal.h", "dx_device.h", "dx_jac.h", "dx_task.h", "dx_mtw.h")
+HEADERS = ("dx_internal.h", "dx_device.h", "dx_jac.h", "dx_task.h", "dx_mtw.h", "dx_host.h")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 DIMS = ("nq", "nv", "nbody", "njnt", "nu", "ntendon", "nsite", "nlevel", "nroot", "nfric", "nlimj", "nlimt",
         "nbpair", "any_damping", "disable_contact", "iterations", "solver", "solimp_pow2")  # dx_device.h DX_DIMS
+
+
+def _sources(csrc: str = None) -> tuple:
+    """Every translation unit of the csrc directory being built: the kernel units and the
+    host units, whichever that revision has (tools/build_variant.py --rev)."""
+    return tuple(sorted(f for f in os.listdir(csrc or CSRC) if f.startswith("dx_") and f.endswith(".hip")))
 
 
 def _stale() -> bool:
     if not os.path.exists(OUT):
         return True
     t = os.path.getmtime(OUT)
-    deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS]
+    deps = [os.path.join(CSRC, s) for s in _sources() + HEADERS]
     deps.append(os.path.join(ROOT, "include", "dx.h"))
     deps += glob.glob(os.path.join(ROOT, "assets", "*.npz"))
     return any(os.path.getmtime(p) > t for p in deps)
@@ -64,7 +68,7 @@ def _spec_names() -> list:
 def _units() -> list:
     """(object name, source, extra flags): every source once, plus dx_step.hip once per
     scene specialization (-DDX_SPEC_ONLY), so the kernels compile in parallel."""
-    units = [(os.path.splitext(s)[0], s, ()) for s in SOURCES]
+    units = [(os.path.splitext(s)[0], s, ()) for s in _sources()]
     # a PGS specialization runs one wave per SIMD: AR's diagonal blocks and the rows' P
     # take ~430 VGPRs (dx_step.hip solve_pgs_ar), which two waves per SIMD would spill
     # (CG too: its launch is bound by its slowest envs' chains, which run faster alone on a
@@ -102,7 +106,7 @@ def source_key(csrc: str = None) -> str:
     (dx_build_key), and _lib.load refuses an in-tree library built from other sources."""
     csrc = csrc or CSRC
     h = hashlib.sha1()
-    for f in sorted(SOURCES + HEADERS + ("dx_specs.inc",)):
+    for f in sorted(_sources(csrc) + HEADERS + ("dx_specs.inc",)):
         path = os.path.join(csrc, f)
         if os.path.exists(path):
             h.update(f.encode() + open(path, "rb").read())
@@ -115,8 +119,9 @@ def _compile_locked(out: str, verbose: bool) -> None:
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     key = source_key()
     jobs, objs = [], []
+    keyed = "dx_model.hip" if "dx_model.hip" in _sources() else "dx_api.hip"  # the unit that defines dx_build_key
     for name, src, extra in _units():
-        if src == "dx_api.hip":
+        if src == keyed:
             extra = extra + (f'-DDX_BUILD_KEY="{key}"',)
         xk = hashlib.sha1(" ".join(extra).encode()).hexdigest()[:6]  # (per-unit flags: DX_PGS_WAVES)
         obj = os.path.join(OBJ, f"{name}.{key}{xk}.o")

@@ -350,7 +350,7 @@ enum { I_NSTEP = 12, I_FLAGS = 13 };
 // position stage
 // ------------------------------------------------------------------------ //
 // Per-body model data of lane b = body (nbody <= 64), loaded in one memory round trip
-// at the start of a tree pass (dx_api.hip body_rec); the level loops then touch only
+// at the start of a tree pass (dx_model.hip body_rec); the level loops then touch only
 // LDS.  Joint fields are the body's first joint (Shadow / Adroit bodies have <= 1).
 struct BodyRec {
   int parent, depth, ja, jn, jtype, qadr, dofadr, dofnum, jdof, rootidx;

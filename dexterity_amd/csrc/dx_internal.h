@@ -30,7 +30,7 @@
 // first step of the shuffle search over a chunk's contacts (5 steps for <= 32 contacts)
 #define DX_SEARCH0 (DX_NCON_MAX > 32 ? 32 : 16)
 #ifndef DX_CAND_MAX
-#define DX_CAND_MAX 768   // collision candidate-list words per env (dx_api.hip LDS layout)
+#define DX_CAND_MAX 768   // collision candidate-list words per env (dx_model.hip lds_layout)
 #endif
 #define DX_DOFMAX 14      // max dofs in a contact Jacobian (|chain(b1) xor chain(b2)|; checked at load)
 #define DX_CON_STRIDE 20  // words per contact record in LDS:
@@ -105,7 +105,7 @@ struct DevModel {
   const DXG float *geom_size, *geom_pos, *geom_mat, *geom_center, *geom_bsphere, *geom_bsphere_b, *geom_obb_b;
   const DXG int *mesh_vertadr, *mesh_vertnum;
   const DXG float4* mesh_vert4;  // hull vertices (x, y, z, index in the mesh as int bits)
-  // direction-binned hulls (dx_api.hip build_hull_bins): cube map of binn x binn cells
+  // direction-binned hulls (dx_model.hip build_hull_bins): cube map of binn x binn cells
   // per face, bincap = DX_HULL_K float4 (x, y, z, vertex index bits; -1 = padding) per cell
   const DXG int *mesh_binn, *mesh_bincap, *mesh_binadr;
   const DXG float4* mesh_bin4;
@@ -113,16 +113,16 @@ struct DevModel {
   // bin_cap, vert4 offset, bin4 offset, -}{size, -}{pos, -}{mat 9, center 3, -};
   // gpair_rec [ngpair] = {g1, g2, margin, primitive-pair flag}
   const DXG float4 *geom_rec, *gpair_rec;
-  // culling records (dx_api.hip): geom_crec [ngeom][6], bpair_rec [nbpair][7] float4
+  // culling records (dx_model.hip): geom_crec [ngeom][6], bpair_rec [nbpair][7] float4
   const DXG float4 *geom_crec, *bpair_rec;
-  // body-pair cull (dx_api.hip): bp_item [nbitem][2] float4, the distinct planes (the first
+  // body-pair cull (dx_model.hip): bp_item [nbitem][2] float4, the distinct planes (the first
   // nbplane) and bounding spheres of the body pairs; bp_cull [nbpair], a pair's two items
   const DXG float4* bp_item;
   const DXG int2* bp_cull;
   int nbitem, nbplane;
-  // tree records (dx_api.hip): body_rec [nbody][8] float4, dof_rec [nv][2] float4
+  // tree records (dx_model.hip): body_rec [nbody][8] float4, dof_rec [nv][2] float4
   const DXG float4 *body_rec, *dof_rec;
-  // tree-sparse LDL^T of M (dx_api.hip): [ldl_nslot][64] items k | i << 8 | j << 16
+  // tree-sparse LDL^T of M (dx_model.hip): [ldl_nslot][64] items k | i << 8 | j << 16
   // (-1: none) grouped by level, bit s of ldl_sync ends a level; nslot 0: dense solver
   int ldl_nslot;
   unsigned ldl_sync;

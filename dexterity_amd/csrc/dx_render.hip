@@ -4,7 +4,7 @@
 // Every input is in the batch arrays once a control step's last launch (or dx_forward) is
 // queued: DX_XPOS / DX_XQUAT (DevBatch::out_bodies, which the setter switches on), plus the
 // model's geom tables and the hull face planes the library derives on the host
-// (dx_api.hip hull_planes).  The step kernels know nothing of this kernel.
+// (dx_model.hip hull_planes).  The step kernels know nothing of this kernel.
 //
 // Layout.  A workgroup of four waves renders one 16 x 16 pixel tile of one (env, camera);
 // a wave's lanes are an 8 x 8 block of the tile, so the rays of a wave stay close and the

@@ -44,7 +44,7 @@ __device__ __forceinline__ void st_sc1_f4(void* base, int nbytes, int off, float
 // ------------------------------------------------------------------------ //
 struct Shape {
   int type, nvert;
-  int bin_n, bin_cap;  // direction-binned hull (bin_n > 0), see dx_api.hip build_hull_bins
+  int bin_n, bin_cap;  // direction-binned hull (bin_n > 0), see dx_model.hip build_hull_bins
   float pos[3], mat[9], size[3], center[3], margin;
   const DXG float4* vert4;  // hull vertices (x, y, z, index) in global memory (L2-resident)
   const DXG float4* bin4;   // this hull's cells
@@ -312,7 +312,7 @@ __device__ __forceinline__ void hull_reduce(const HullBest& h, float* lp) {
   lp[1] = __int_as_float(row_or_i<NPG>(win ? __float_as_int(h.y) : 0));
   lp[2] = __int_as_float(row_or_i<NPG>(win ? __float_as_int(h.z) : 0));
 }
-// Cube-map cell of local direction ld (host twin: dx_api.hip cell_corners).  Returns
+// Cube-map cell of local direction ld (host twin: dx_model.hip cell_corners).  Returns
 // -1 for a zero direction (then the whole hull is scanned, as the oracle does).  No
 // branch: every lane computes a cell and selects -1 after.
 __device__ __forceinline__ int hull_cell(const float* ld, int n) {
@@ -332,7 +332,7 @@ __device__ __forceinline__ int hull_cell(const float* ld, int n) {
   return nz ? (face * n + iu) * n + iv : -1;
 }
 // One hull's support scan by a lane group.  First a DX_HULL_K-slot block -- the
-// direction's cube-map cell (dx_api.hip build_hull_bins), or the first K vertices of a
+// direction's cube-map cell (dx_model.hip build_hull_bins), or the first K vertices of a
 // hull that is not binned / a zero direction -- one 128-B line, one memory round trip;
 // then, rarely, an overflow run: the rest of a cell whose slot K - 1 is a header, or the
 // rest of a whole-hull scan.
@@ -999,7 +999,7 @@ __device__ __forceinline__ int narrow_pass(const Ctx& c, int ng, const int* gcan
     MprState M;
     bool cached = false;
     int trips = 0;
-    M.P = c.f(c.L.cand + c.L.cand_max) + MP_WORDS * grp;  // free during collision (dx_api.hip layout)
+    M.P = c.f(c.L.cand + c.L.cand_max) + MP_WORDS * grp;  // free during collision (dx_model.hip lds_layout)
     const NpClock ck{c.stage_acc, c.I};
     for (;;) {
       bool act = q < ng;
@@ -1117,7 +1117,7 @@ __device__ __forceinline__ void collision(const Ctx& c, int watch_only, int wg, 
   float* xmat = c.f(c.L.xmat);
   // 1. body-pair cull -> cand[0..nbc) body-pair ids, pref[0..nbc] prefix of geom-pair counts.
   // Bounding spheres (and planes) over all body pairs, lane per pair; the survivors go
-  // to a list, and one pass over the list applies the box test (dx_api.hip bpair_rec)
+  // to a list, and one pass over the list applies the box test (dx_model.hip bpair_rec)
   // and compacts: the box SAT then runs on ~1 chunk of survivors, not on every chunk.
   int half = cmax / 3;
   int* pref = cand + half;
@@ -1158,7 +1158,7 @@ __device__ __forceinline__ void collision(const Ctx& c, int watch_only, int wg, 
     nsl = 0;
     SYNC();
   };
-  // The pairs of a scene share a few bounding spheres and one ground plane (dx_api.hip
+  // The pairs of a scene share a few bounding spheres and one ground plane (dx_model.hip
   // bp_item), so each distinct one goes to the world once per pass, lane per item, into
   // the narrowphase's portal area -- unused until the narrowphase, between the lists
   // flush() writes and sl: item i at float4 i (a sphere's centre and radius, a plane's
@@ -1274,7 +1274,7 @@ __device__ __forceinline__ void collision(const Ctx& c, int watch_only, int wg, 
   int* gcand = pref + half;
   int gmax = cmax - 2 * half;
   // pair records of the surviving candidates, after the four groups' portal points
-  // (dx_api.hip layout reserves 4 * gmax words there)
+  // (dx_model.hip lds_layout reserves 4 * gmax words there)
   float4* gcrec = (float4*)(c.f(c.L.cand + c.L.cand_max) + DX_NGRP_MAX * MP_WORDS);
   int ng = 0;
   int total = nbc > 0 ? pref[nbc] : 0;
@@ -1841,7 +1841,7 @@ __device__ __forceinline__ void velocity_stage(const Ctx& c, const float* xfrc, 
   const float a_wc0 = a_wn > 0 ? m.wrap_coef[a_wa] : 0.f, a_wc1 = a_wn > 1 ? m.wrap_coef[a_wa + 1] : 0.f;
   const int a_wd0 = a_wn > 0 ? m.wrap_dof[a_wa] : 0, a_wd1 = a_wn > 1 ? m.wrap_dof[a_wa + 1] : 0;
   // The tree recursions of mj_comVel / mj_rne are sums over a body's dof chain (the
-  // dofs on its path to the root, dx_api.hip body_chain), so every dof and every body
+  // dofs on its path to the root, dx_model.hip body_chain), so every dof and every body
   // is computed at once instead of one tree level after another:
   //   cdof_dot[d] = (sum of cdof[e] qvel[e] over the chain dofs e before d) x cdof[d]
   //   cvel[b]     = sum over chain(b) of cdof[e] qvel[e]
@@ -3530,7 +3530,7 @@ template <class Ctx>
 __device__ __forceinline__ void forward(const Ctx& c, const float* xfrc, int xfrc_stride, int env) {
   const DevModel& m = c.mdl();
   int nv = c.nv;
-  // Stage order (LDS phases, see dx_api.hip layout): kinematics/com/crb and the
+  // Stage order (LDS phases, see dx_model.hip lds_layout): kinematics/com/crb and the
   // velocity stage use the com temporaries; the smooth solve reuses them for its
   // transpose; collision reuses them for candidates + hull staging; the constraint
   // rows and contact jacobians overwrite those; the Newton Hessian overwrites the
@@ -4751,7 +4751,7 @@ DX_SPEC_DEFINE1(DX_SPEC_ONLY)
 #else
 DX_SPECS(DX_SPEC_FNS)
 
-// The model struct is read through a device pointer (dx_api.hip device_model) in
+// The model struct is read through a device pointer (dx_batch.hip device_model) in
 // the constant address space rather than passed by value in the kernarg segment.
 extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DX_STEP_WAVES)))
 dx_step_kernel(const DevModel* __restrict__ mp, DevBatch B, Lds L, int nsub, int mode) {

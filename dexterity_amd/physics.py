@@ -338,7 +338,7 @@ class BatchedPhysics:
             _lib.check(_lib.load().dx_debug_get(self.ptr, name.encode(), out.ctypes.data, 1))
             return out
         if name in ("bp_sizes", "bp_item", "bp_cull"):
-            # the body-pair cull's host tables (dx_api.hip): {nbitem, nbplane, nbpair}, the
+            # the body-pair cull's host tables (dx_model.hip): {nbitem, nbplane, nbpair}, the
             # distinct planes and spheres [nbitem][8], a pair's items and margin [nbpair][2]
             out = np.zeros(3, dtype=np.int32)
             _lib.check(_lib.load().dx_debug_get(self.ptr, b"bp_sizes", out.ctypes.data, 3))

@@ -4,7 +4,7 @@ wave linear algebra and reductions (tests/csrc/dx_linalg_harness.hip).
 build() compiles the harness twice with dexterity_amd/build.py's own FLAGS, once with
 -DDX_LANE_RANGE_MASK=0 (the lane id as dx_ik / dx_dls see it) and once with 0x3b (as
 dx_step.hip sees it), into tests/_build/libdx_linalg_harness_{plain,ranged}.so.  The
-harness is not one of build.py's SOURCES: libdx.so and its build key do not depend on it.
+harness is not in build.py's csrc directory: libdx.so and its build key do not depend on it.
 
 The references are the fp32 restatements of the same algorithms (tests/test_sweep_solve.py,
 tests/test_tree_ldl.py, an fp32 Cholesky with two substitutions); fp64 numpy is the truth.
@@ -217,7 +217,7 @@ def asset_trees(min_nv: int = 31) -> dict:
 
 
 def ldl_table(par):
-    """(nslot, sync, tab[DX_LDL_SLOTS * 64]) as dx_api.hip builds them, from ldl_slots."""
+    """(nslot, sync, tab[DX_LDL_SLOTS * 64]) as dx_model.hip builds them, from ldl_slots."""
     slots, ends = ldl_slots(par)
     tab = np.full(DX_LDL_SLOTS * WAVE, -1, np.int32)
     sync = 0

@@ -80,7 +80,7 @@ def test_null_arguments_are_rejected(lib):
 
 @pytest.mark.parametrize("asset", ["shadow_reorient", "adroit_reach"])
 def test_binned_hull_support_matches_full_scan(lib, asset):
-    """Direction-binned hulls (dx_api.hip build_hull_bins) return the vertex the full
+    """Direction-binned hulls (dx_model.hip build_hull_bins) return the vertex the full
     serial scan returns -- the first maximiser -- for random and axis-aligned
     directions, including cell edges and faces.  A different index is accepted only
     for a tie at fp32 resolution (two vertices whose fp64 dots differ by < 1e-6 R,

@@ -1,5 +1,5 @@
 """The body-pair cull transforms each distinct bounding sphere and plane once per pass
-(dx_api.hip bp_item / bp_cull, dx_step.hip collision step 1).  The host tables must expand
+(dx_model.hip bp_item / bp_cull, dx_step.hip collision step 1).  The host tables must expand
 back to the pair arrays of the compiled model bit for bit, and stepping must give exactly
 what the per-pair loop of the parent revision gave (tests/golden/broadphase_parent.npz,
 recorded by tools/record_broadphase_golden.py with the parent's library)."""

@@ -55,7 +55,7 @@ def tree_cases():
     for name, par in trees.items():
         tab = lh.ldl_table(par)
         if tab[0] > lh.DX_LDL_SLOTS:
-            continue  # the model would keep the dense solver (dx_api.hip)
+            continue  # the model would keep the dense solver (dx_model.hip)
         names.append(name)
         slots, _ = lh.ldl_slots(par)
         for s in lh.tree_systems(name, par):

@@ -1,5 +1,5 @@
 """CPU restatement of the tree-sparse LDL^T solve of M and M + h D (dx_device.h
-tree_solve, item table built by dx_api.hip dx_model_load; MuJoCo's mj_factorM /
+tree_solve, item table built by dx_model.hip ldl_table; MuJoCo's mj_factorM /
 mj_solveM [3P]).  For every shipped scene: the elimination items grouped by height
 level, applied slot by slot with every slot's reads taken before its writes (what the
 wave does with LDS atomics), then the two substitution chains with the kernel's
@@ -17,7 +17,7 @@ WAVE = 64
 
 
 def ldl_slots(par):
-    """Items (k, i, j) per 64-lane slot, level by level (dx_api.hip ldl_tab)."""
+    """Items (k, i, j) per 64-lane slot, level by level (dx_model.hip ldl_table)."""
     nv = len(par)
     height = [0] * nv
     for k in range(nv - 1, -1, -1):
