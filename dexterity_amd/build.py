@@ -58,17 +58,23 @@ OBJ = os.path.join(ROOT, "build", "obj")
 SOLVER_SPECS = ("shadow_reorient",)  # scenes specialised for CG and PGS too (spec_text)
 
 
-def _spec_names() -> list:
-    if not os.path.exists(SPECS):
+PROF_FLAG = "-DDX_PROF=1"  # the instrumented twin of a dx_step.hip unit (dx_device.h DX_PROF)
+
+
+def _spec_names(csrc: str = None) -> list:
+    specs = os.path.join(csrc, "dx_specs.inc") if csrc else SPECS
+    if not os.path.exists(specs):
         return []
-    m = re.search(r"#define DX_SPECS\(X\)(.*)", open(SPECS).read())
+    m = re.search(r"#define DX_SPECS\(X\)(.*)", open(specs).read())
     return re.findall(r"X\((\w+)\)", m.group(1)) if m else []
 
 
-def _units() -> list:
+def _units(csrc: str = None) -> list:
     """(object name, source, extra flags): every source once, plus dx_step.hip once per
-    scene specialization (-DDX_SPEC_ONLY), so the kernels compile in parallel."""
-    units = [(os.path.splitext(s)[0], s, ()) for s in _sources()]
+    scene specialization (-DDX_SPEC_ONLY), so the kernels compile in parallel; then every
+    dx_step.hip unit once more with the stage profiler compiled in (PROF_FLAG), the twin
+    that a batch with stage timing on launches."""
+    units = [(os.path.splitext(s)[0], s, ()) for s in _sources(csrc)]
     # a PGS specialization runs one wave per SIMD: AR's diagonal blocks and the rows' P
     # take ~430 VGPRs (dx_step.hip solve_pgs_ar), which two waves per SIMD would spill
     # (CG too: its launch is bound by its slowest envs' chains, which run faster alone on a
@@ -81,11 +87,14 @@ def _units() -> list:
         w = next((v for k, v in waves.items() if n.endswith(k) and v), None)
         return (f"-DDX_SPEC_ONLY={n}",) + ((f"-DDX_STEP_WAVES={w}",) if w else ())
 
-    units += [(f"dx_step_{n}", "dx_step.hip", spec_flags(n)) for n in _spec_names()]
+    units += [(f"dx_step_{n}", "dx_step.hip", spec_flags(n)) for n in _spec_names(csrc)]
     # the overflow tier: the step kernel's physics with the DX_NCON_HI contact pool
     units.append(("dx_step_hi", "dx_step.hip", ("-DDX_TIER_HI", "-DDX_NCON_MAX=DX_NCON_HI")))
     # the mid tier: the same physics with the DX_NCON_MID pool, beside queued launches
     units.append(("dx_step_mid", "dx_step.hip", ("-DDX_TIER_MID", "-DDX_NCON_MAX=DX_NCON_MID")))
+    # (the sources of a revision from before the switch have no twins: tools/build_variant.py --rev)
+    if "DX_PROF" in open(os.path.join(csrc or CSRC, "dx_device.h")).read():
+        units += [(f"{n}_prof", src, extra + (PROF_FLAG,)) for n, src, extra in units if src == "dx_step.hip"]
     return units
 
 
@@ -102,8 +111,9 @@ def _compile(out: str, verbose: bool) -> None:
 
 def source_key(csrc: str = None) -> str:
     """Hash of everything a libdx.so is built from (sources, headers, the scene
-    specializations, the C ABI header, the flags).  The library carries it
-    (dx_build_key), and _lib.load refuses an in-tree library built from other sources."""
+    specializations, the C ABI header, the flags, every unit's own flags: the profiler twins',
+    DX_*_WAVES).  The library carries it (dx_build_key), and _lib.load refuses an in-tree
+    library built from other sources."""
     csrc = csrc or CSRC
     h = hashlib.sha1()
     for f in sorted(_sources(csrc) + HEADERS + ("dx_specs.inc",)):
@@ -112,6 +122,8 @@ def source_key(csrc: str = None) -> str:
             h.update(f.encode() + open(path, "rb").read())
     h.update(open(os.path.join(ROOT, "include", "dx.h"), "rb").read())
     h.update(" ".join(FLAGS).encode())
+    for name, _, extra in _units(csrc):
+        h.update(f"\n{name} {' '.join(extra)}".encode())
     return h.hexdigest()[:16]
 
 
@@ -120,7 +132,8 @@ def _compile_locked(out: str, verbose: bool) -> None:
     key = source_key()
     jobs, objs = [], []
     keyed = "dx_model.hip" if "dx_model.hip" in _sources() else "dx_api.hip"  # the unit that defines dx_build_key
-    for name, src, extra in _units():
+    # the dx_step.hip units first: each takes minutes, the host units seconds
+    for name, src, extra in sorted(_units(), key=lambda u: u[1] != "dx_step.hip"):
         if src == keyed:
             extra = extra + (f'-DDX_BUILD_KEY="{key}"',)
         xk = hashlib.sha1(" ".join(extra).encode()).hexdigest()[:6]  # (per-unit flags: DX_PGS_WAVES)
@@ -137,7 +150,7 @@ def _compile_locked(out: str, verbose: bool) -> None:
         os.replace(cmd[-1], obj)
 
     nproc = int(os.environ.get("MAX_JOBS", os.cpu_count() or 4))
-    with concurrent.futures.ThreadPoolExecutor(max_workers=max(1, min(nproc, 8))) as ex:
+    with concurrent.futures.ThreadPoolExecutor(max_workers=max(1, min(nproc, 16))) as ex:
         for f in [ex.submit(run, j) for j in jobs]:
             f.result()
     cmd = [hipcc, f"--offload-arch={ARCH}", "-fPIC", "-shared", *objs, "-L/opt/rocm/lib", "-lrccl", "-o", out]

@@ -108,6 +108,21 @@ int balloc(dx_batch* b, void** p, size_t bytes) {
   return 0;
 }
 
+// Sets b->slots, the chip's resident 64-lane workgroups of the step kernel the batch
+// launches (the instrumented twin's with stage timing on), and returns the count per CU
+// (LDS and VGPR limits; 8 when the runtime cannot say), with the occupancy experiment
+// DX_LDS_PAD (extra LDS bytes).
+static int step_slots(dx_batch* b) {
+  int ncu = 0;
+  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, b->device) != hipSuccess || ncu < 1) ncu = 256;
+  const char* pad = getenv("DX_LDS_PAD");
+  const size_t lds = (size_t)b->model->lds.total * 4 + (pad ? (size_t)atol(pad) : 0);
+  int per = dx_step_occupancy(b->spec, lds, b->db.stage_acc != nullptr);
+  if (per < 1) per = (int)std::max<size_t>(1, std::min<size_t>(8, 163840 / lds));
+  b->slots = ncu * per;
+  return per;
+}
+
 extern "C" dx_batch* dx_batch_create(const dx_model* mc, int32_t nenv, int32_t device) {
   dx_model* m = const_cast<dx_model*>(mc);
   if (!m || nenv < 1) { dx_fail(DX_EINVAL, "bad model or nenv"); return nullptr; }
@@ -183,18 +198,12 @@ extern "C" dx_batch* dx_batch_create(const dx_model* mc, int32_t nenv, int32_t d
   B.order_last = getenv("DX_ORDER_LAST") ? atoi(getenv("DX_ORDER_LAST")) : 1;
   b->hi_grid = getenv("DX_HI_GRID") ? std::max(1, atoi(getenv("DX_HI_GRID"))) : DX_HI_GRID;
   {
-    int ncu = 0;
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || ncu < 1) ncu = 256;
-    // resident 64-lane workgroups of the step kernel per CU (LDS and VGPR limits; 8 when
-    // the runtime cannot say), plus the occupancy experiment DX_LDS_PAD (extra LDS bytes)
-    const char* pad = getenv("DX_LDS_PAD");
-    const size_t lds = (size_t)m->lds.total * 4 + (pad ? (size_t)atol(pad) : 0);
-    int per = dx_step_occupancy(b->spec, lds);
-    if (per < 1) per = (int)std::max<size_t>(1, std::min<size_t>(8, 163840 / lds));
-    b->slots = ncu * per;
+    const int per = step_slots(b);
     // the mid tier: its workgroup fits a CU that holds one step-kernel workgroup fewer
     // (LDS in 512-B granules; its VGPRs fit the SIMD that then runs one wave)
     auto g512 = [](size_t x) { return (x + 511) / 512 * 512; };
+    const char* pad = getenv("DX_LDS_PAD");
+    const size_t lds = (size_t)m->lds.total * 4 + (pad ? (size_t)atol(pad) : 0);
     const size_t lmid = (size_t)m->lds_mid.total * 4;
     b->mid = b->queue && B.defer && m->lds_mid.nefc_max > 0 && !getenv("DX_NO_MID") && per >= 2 &&
              (size_t)(per - 1) * g512(lds) + g512(lmid) <= 163840;
@@ -803,6 +812,9 @@ extern "C" int dx_stage_timing(dx_batch* b, int enable) {
   } else if (!enable) {
     b->db.stage_acc = nullptr;
   }
+  // the launches now run the instrumented twins (on) or the production kernels (off): the
+  // queue's persistent grid is the occupancy of the kernel it launches
+  step_slots(b);
   return 0;
 }
 

@@ -251,6 +251,24 @@ __device__ __forceinline__ float dot6(const float* a, const float* b) {
 struct SpecRT {
   static constexpr bool reach_task = false;  // (the generic kernel: no fused reach sampling pass)
 };
+// DX_PROF: the per-stage profiler is a compile-time switch.  build.py compiles every
+// dx_step.hip unit twice: the production kernels without it (the context then has no
+// stage_acc member, c.acc() is a constant null, and stage_mark, stage_count, the
+// narrowphase's counters and the queue's wait clock are no code at all), and instrumented
+// twins with -DDX_PROF=1, which the launchers pick exactly when DevBatch::stage_acc is set
+// (dx_stage_timing).
+#ifndef DX_PROF
+#define DX_PROF 0
+#endif
+#if DX_PROF
+#define DX_PROF_MEMBER           \
+  unsigned long long* stage_acc; \
+  __device__ unsigned long long* acc() const { return stage_acc; }
+#define DX_PROF_INIT(a) , stage_acc(a)
+#else
+#define DX_PROF_MEMBER __device__ static constexpr unsigned long long* acc() { return nullptr; }
+#define DX_PROF_INIT(a)
+#endif
 // Stages take the model through c.mdl().  (Laundering that reference per stage, so
 // each stage re-loads its table pointers instead of the kernel keeping ~100 of them
 // live, cut the SGPR spills 408 -> 331 but not the step time; it is a plain
@@ -265,13 +283,13 @@ struct CtxT {
 #undef DX_X
   float* S;
   int* I;  // misc ints
-  unsigned long long* stage_acc;
+  DX_PROF_MEMBER
   float4* sep = nullptr;  // this env's separating-direction cache (DX_SEP_SLOTS), or null
   int np_wide = DX_WAVE / 8;  // narrowphase: 4-lane groups above this many candidates
   bool defer = false;         // a full contact pool defers the physics step (I_DEFER)
   int defer_at = DX_NCON_MAX; // ... or more contacts than this (DX_DEFER_AT: tests, probes)
   __device__ CtxT(const DevModel& m_, const Lds&, float* S_, int* I_, unsigned long long* acc)
-      : m(m_), S(S_), I(I_), stage_acc(acc) {}
+      : m(m_), S(S_), I(I_) DX_PROF_INIT(acc) {}
   __device__ float* f(int off) const { return S + off; }
   __device__ const DevModel& mdl() const { return m; }
 };
@@ -285,7 +303,7 @@ struct CtxT<SpecRT> {
 #undef DX_X
   float* S;
   int* I;
-  unsigned long long* stage_acc;
+  DX_PROF_MEMBER
   float4* sep = nullptr;
   int np_wide = DX_WAVE / 8;
   bool defer = false;
@@ -295,11 +313,11 @@ struct CtxT<SpecRT> {
 #define DX_X(n) n(m_.n),
         DX_DIMS(DX_X)
 #undef DX_X
-        S(S_), I(I_), stage_acc(acc) {}
+        S(S_), I(I_) DX_PROF_INIT(acc) {}
   __device__ float* f(int off) const { return S + off; }
   __device__ const DevModel& mdl() const { return m; }
 };
-// Per-stage cycle accounting (runtime-gated by DevBatch::stage_acc, lane 0 only).
+// Per-stage cycle accounting (DX_PROF builds; runtime-gated by DevBatch::stage_acc, lane 0 only).
 enum {
   ST_KIN = 0, ST_CRB, ST_BROAD, ST_MID, ST_NARROW, ST_CON, ST_VEL, ST_SMOOTH, ST_NEWTON_EVAL,
   ST_NEWTON_GRAD, ST_NEWTON_HESS, ST_NEWTON_CHOL, ST_NEWTON_LS, ST_QFRC, ST_EULER, ST_OBSERVE, ST_IO,
@@ -322,10 +340,10 @@ __device__ __forceinline__ void stage_add(P p, unsigned long long v) {
 }
 template <class Ctx>
 __device__ __forceinline__ void stage_mark(const Ctx& c, int k) {
-  if (c.stage_acc && LANE == 0) {
+  if (DX_PROF && c.acc() && LANE == 0) {
     unsigned long long t = __builtin_amdgcn_s_memtime();
     unsigned long long* last = (unsigned long long*)(c.I + 10);
-    stage_add(c.stage_acc + k, t - *last);
+    stage_add(c.acc() + k, t - *last);
     *last = t;
   }
 }
@@ -334,7 +352,7 @@ __device__ __forceinline__ void stage_mark(const Ctx& c, int k) {
 #endif
 template <class Ctx>
 __device__ __forceinline__ void stage_count(const Ctx& c, int k, int n = 1) {
-  if (c.stage_acc && LANE == 0) stage_add(c.stage_acc + k, (unsigned long long)n);
+  if (DX_PROF && c.acc() && LANE == 0) stage_add(c.acc() + k, (unsigned long long)n);
 }
 // misc int slots
 // I_OVF: capacity bits of the substep (1 candidates, 2 contacts, 4 Jacobian dofs, 8 rows);

@@ -490,17 +490,21 @@ __device__ __forceinline__ float dx_urand(uint64_t seed, int env, int episode, i
 // dx_step.hip: specialized-kernel lookup and launch (host side)
 int dx_spec_find(const DevModel& d, const Lds& L);
 bool dx_spec_reach(int spec);  // the specialization fuses the reach sampling pass
-int dx_step_occupancy(int spec, size_t lds);
+int dx_step_occupancy(int spec, size_t lds, bool prof);  // prof: of the instrumented twin (DX_PROF)
 hipError_t dx_launch_step(int spec, int grid, size_t lds, hipStream_t stream, const DevModel* mdev, const DevBatch& B,
                           const Lds& L, int nsub, int mode);
 hipError_t dx_launch_order(int nenv, hipStream_t stream, const unsigned* cost, int* order, unsigned* qhead);
 // the overflow tier (dx_step.hip, DX_TIER_HI): the physics steps deferred by the last launch
 hipError_t dx_launch_step_hi(int grid, size_t lds, hipStream_t stream, const DevModel* mdev, const DevBatch& B,
                              const Lds& L, int nsub);
+hipError_t dx_launch_step_hi_prof(int grid, size_t lds, hipStream_t stream, const DevModel* mdev, const DevBatch& B,
+                                  const Lds& L, int nsub);  // (its twin; dx_launch_step_hi picks it)
 // the mid tier (dx_step.hip, DX_TIER_MID): beside the queued launch after which qdone[0]
 // reaches `target`
 hipError_t dx_launch_step_mid(int grid, size_t lds, hipStream_t stream, const DevModel* mdev, const DevBatch& B,
                               const Lds& L, int nsub, unsigned target);
+hipError_t dx_launch_step_mid_prof(int grid, size_t lds, hipStream_t stream, const DevModel* mdev, const DevBatch& B,
+                                   const Lds& L, int nsub, unsigned target);  // (its twin)
 
 // dx_sensor.hip: joint torque sensors and contact force sensing from the step kernel's
 // stash (host side).  Every output is optional: `out` (the torque sensors) and the two of

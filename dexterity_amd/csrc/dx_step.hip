@@ -1000,7 +1000,7 @@ __device__ __forceinline__ int narrow_pass(const Ctx& c, int ng, const int* gcan
     bool cached = false;
     int trips = 0;
     M.P = c.f(c.L.cand + c.L.cand_max) + MP_WORDS * grp;  // free during collision (dx_model.hip lds_layout)
-    const NpClock ck{c.stage_acc, c.I};
+    const NpClock ck{c.acc(), c.I};
     for (;;) {
       bool act = q < ng;
       if (__ballot(act) == 0) break;
@@ -1090,7 +1090,7 @@ __device__ __forceinline__ int narrow_pass(const Ctx& c, int ng, const int* gcan
     stage_count(c, CNT_NP_TRIPS, trips);
   }
   SYNC();
-  if (c.stage_acc) {
+  if (DX_PROF && c.acc()) {
     bool lead = SL == 0;
     int v[7] = {st.plane_box, st.plane_convex, st.capsule, st.mpr, st.support, st.hit, st.maxit};
 #pragma unroll
@@ -3876,7 +3876,7 @@ __device__ __forceinline__ float env_begin(Ctx& c, const DevBatch& B, int env, c
 #endif
   SYNC();
   int* I = c.I;
-  if (c.stage_acc && LANE == 0) *(unsigned long long*)(I + 10) = __builtin_amdgcn_s_memtime();
+  if (DX_PROF && c.acc() && LANE == 0) *(unsigned long long*)(I + 10) = __builtin_amdgcn_s_memtime();
   float* qpos = c.f(L.qpos);
   float* qvel = c.f(L.qvel);
   float* ctrl = c.f(L.ctrl);
@@ -4238,6 +4238,9 @@ __device__ __forceinline__ float fused_reach_prep(Ctx& c, const DevBatch& B, int
   return env_begin(c, B, env);
 }
 
+// The batch's stage accumulators: a constant null outside a DX_PROF build.
+__device__ __forceinline__ unsigned long long* prof_acc(const DevBatch& B) { return DX_PROF ? B.stage_acc : nullptr; }
+
 // What every driver below does with a context before an env's first stage: the block's
 // integers, the env's separating-direction cache, the narrowphase width and, for a driver
 // that profiles (`prof`), the env's stage accumulators.  The deferral policy (defer,
@@ -4247,7 +4250,11 @@ __device__ __forceinline__ void ctx_bind_env(Ctx& c, const DevBatch& B, int env,
   c.I = (int*)(c.S + c.L.ints);
   c.sep = B.sepcache ? B.sepcache + (size_t)env * DX_SEP_SLOTS : nullptr;
   c.np_wide = B.np_wide;
+#if DX_PROF
   if (prof) c.stage_acc = B.stage_acc ? B.stage_acc + (size_t)env * DX_NSTAGE : nullptr;
+#else
+  (void)prof;
+#endif
 }
 
 // The tiers' run of an env they took over: its physics steps s0 .. nsub - 1, up to the end of
@@ -4379,7 +4386,7 @@ __device__ __forceinline__ void step_queue(const DevModel& m, const DevBatch& B,
       int abort = 0;
       if (LANE == 0) {
         unsigned n = 0;
-        const unsigned long long w0 = B.stage_acc ? __builtin_amdgcn_s_memtime() : 0ull;
+        const unsigned long long w0 = prof_acc(B) ? __builtin_amdgcn_s_memtime() : 0ull;
         for (;;) {
           const unsigned tag = __hip_atomic_load(B.progress + env, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           if (tag == qtag(B.epoch, s)) break;
@@ -4402,7 +4409,7 @@ __device__ __forceinline__ void step_queue(const DevModel& m, const DevBatch& B,
           }
         }
         // (profiling: the cycles this slot waited for the env's previous physics step)
-        if (B.stage_acc) stage_add(B.stage_acc + (size_t)env * DX_NSTAGE + CNT_QWAIT, __builtin_amdgcn_s_memtime() - w0);
+        if (prof_acc(B)) stage_add(prof_acc(B) + (size_t)env * DX_NSTAGE + CNT_QWAIT, __builtin_amdgcn_s_memtime() - w0);
       }
       if (__builtin_amdgcn_readfirstlane(abort)) continue;  // drain (or deferred / done): later claims end the loop
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
@@ -4450,7 +4457,7 @@ __device__ __forceinline__ void step_queue(const DevModel& m, const DevBatch& B,
     // Profiling runs also carry stage_acc across tasks with plain stores: those keep
     // the release.
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (B.stage_acc) {
+    if (prof_acc(B)) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -4477,6 +4484,17 @@ __device__ __forceinline__ void step_queue(const DevModel& m, const DevBatch& B,
 #define DX_SPECS(X)
 #endif
 
+// The instrumented twins (build.py compiles every unit of this file once more with
+// -DDX_PROF=1): the same kernels and launchers under names of their own, and nothing else
+// of the unit.  The production launchers hand a batch with DevBatch::stage_acc set to them.
+#if DX_PROF
+#define DX_PN(n) n##_prof
+#define DX_PF(base, SP) base##_prof_##SP
+#else
+#define DX_PN(n) n
+#define DX_PF(base, SP) base##_##SP
+#endif
+
 #ifndef DX_STEP_WAVES
 #define DX_STEP_WAVES 2  // waves per SIMD the VGPR budget is set for (3: <= 168 VGPRs, measured slower)
 #endif
@@ -4486,13 +4504,13 @@ __device__ __forceinline__ void step_queue(const DevModel& m, const DevBatch& B,
 // instruction cache.
 template <class SP>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DX_STEP_WAVES)))
-dx_step_kernel_spec(const DevModel* __restrict__ mp, DevBatch B, Lds L, int nsub, int mode) {
+DX_PN(dx_step_kernel_spec)(const DevModel* __restrict__ mp, DevBatch B, Lds L, int nsub, int mode) {
   const DevModel& m = *(const DevModel*)(const DXG DevModel*)mp;
   step_body<SP>(m, B, L, nsub, mode);
 }
 template <class SP>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DX_STEP_WAVES)))
-dx_step_kernel_queue_spec(const DevModel* __restrict__ mp, DevBatch B, Lds L, int nsub) {
+DX_PN(dx_step_kernel_queue_spec)(const DevModel* __restrict__ mp, DevBatch B, Lds L, int nsub) {
   const DevModel& m = *(const DevModel*)(const DXG DevModel*)mp;
   step_queue<SP>(m, B, L, nsub);
 }
@@ -4500,7 +4518,7 @@ dx_step_kernel_queue_spec(const DevModel* __restrict__ mp, DevBatch B, Lds L, in
 // sampling code does not share the step kernel's register allocation.
 template <class SP>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2)))
-dx_prep_kernel_spec(const DevModel* __restrict__ mp, DevBatch B, Lds L) {
+DX_PN(dx_prep_kernel_spec)(const DevModel* __restrict__ mp, DevBatch B, Lds L) {
   const DevModel& m = *(const DevModel*)(const DXG DevModel*)mp;
   step_body<SP>(m, B, L, 1, 2, true);
 }
@@ -4517,8 +4535,11 @@ static bool spec_matches(const DevModel& d, const Lds& L) {
 #define DX_SPEC_FNS(SP)                                                                               \
   bool dx_match_##SP(const DevModel& d, const Lds& L);                                                \
   int dx_occ_##SP(size_t lds);                                                                        \
+  int dx_occ_prof_##SP(size_t lds);                                                                   \
   hipError_t dx_launch_##SP(int grid, size_t lds, hipStream_t stream, const DevModel* m, const DevBatch& B, \
-                            const Lds& L, int nsub, int mode);
+                            const Lds& L, int nsub, int mode);                                        \
+  hipError_t dx_launch_prof_##SP(int grid, size_t lds, hipStream_t stream, const DevModel* m, const DevBatch& B, \
+                                 const Lds& L, int nsub, int mode);
 
 #if defined(DX_TIER_HI)
 // ------------------------------------------------------------------------ //
@@ -4535,7 +4556,7 @@ static_assert(DX_NCON_MAX == DX_NCON_HI, "the overflow tier is compiled with the
 // slice of the envs, from the bucket prefix it computes itself -- and its last workgroup
 // zeroes that histogram and the substep-queue heads for the next step-kernel launch.
 extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1)))
-dx_step_hi_kernel(const DevModel* __restrict__ mp, DevBatch B, Lds L, int nsub) {
+DX_PN(dx_step_hi_kernel)(const DevModel* __restrict__ mp, DevBatch B, Lds L, int nsub) {
   extern __shared__ float smem[];
   const DevModel& m = *(const DevModel*)(const DXG DevModel*)mp;
   // 1. the order: bucket prefix (four buckets per lane), then this workgroup's envs
@@ -4636,14 +4657,17 @@ dx_step_hi_kernel(const DevModel* __restrict__ mp, DevBatch B, Lds L, int nsub) 
   }
 }
 
-hipError_t dx_launch_step_hi(int grid, size_t lds, hipStream_t stream, const DevModel* m, const DevBatch& B,
-                             const Lds& L, int nsub) {
+hipError_t DX_PN(dx_launch_step_hi)(int grid, size_t lds, hipStream_t stream, const DevModel* m, const DevBatch& B,
+                                    const Lds& L, int nsub) {
+#if !DX_PROF
+  if (B.stage_acc) return dx_launch_step_hi_prof(grid, lds, stream, m, B, L, nsub);
+#endif
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)dx_step_hi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)DX_PN(dx_step_hi_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
-  hipLaunchKernelGGL(dx_step_hi_kernel, dim3(grid), dim3(64), lds, stream, m, B, L, nsub);
+  hipLaunchKernelGGL(DX_PN(dx_step_hi_kernel), dim3(grid), dim3(64), lds, stream, m, B, L, nsub);
   return hipGetLastError();
 }
 #elif defined(DX_TIER_MID)
@@ -4666,7 +4690,7 @@ hipError_t dx_launch_step_hi(int grid, size_t lds, hipStream_t stream, const Dev
 // ------------------------------------------------------------------------ //
 static_assert(DX_NCON_MAX == DX_NCON_MID, "the mid tier is compiled with the DX_NCON_MID pool");
 extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2)))
-dx_step_mid_kernel(const DevModel* __restrict__ mp, DevBatch B, Lds L, int nsub, unsigned target) {
+DX_PN(dx_step_mid_kernel)(const DevModel* __restrict__ mp, DevBatch B, Lds L, int nsub, unsigned target) {
   extern __shared__ float smem[];
   const DevModel& m = *(const DevModel*)(const DXG DevModel*)mp;
   for (unsigned i = 0;;) {
@@ -4723,59 +4747,82 @@ dx_step_mid_kernel(const DevModel* __restrict__ mp, DevBatch B, Lds L, int nsub,
   }
 }
 
-hipError_t dx_launch_step_mid(int grid, size_t lds, hipStream_t stream, const DevModel* m, const DevBatch& B,
-                              const Lds& L, int nsub, unsigned target) {
-  hipLaunchKernelGGL(dx_step_mid_kernel, dim3(grid), dim3(64), lds, stream, m, B, L, nsub, target);
+hipError_t DX_PN(dx_launch_step_mid)(int grid, size_t lds, hipStream_t stream, const DevModel* m, const DevBatch& B,
+                                     const Lds& L, int nsub, unsigned target) {
+#if !DX_PROF
+  if (B.stage_acc) return dx_launch_step_mid_prof(grid, lds, stream, m, B, L, nsub, target);
+#endif
+  hipLaunchKernelGGL(DX_PN(dx_step_mid_kernel), dim3(grid), dim3(64), lds, stream, m, B, L, nsub, target);
   return hipGetLastError();
 }
 #elif defined(DX_SPEC_ONLY)
+#if DX_PROF
+#define DX_SPEC_MATCH(SP)
+#else
+#define DX_SPEC_MATCH(SP) bool dx_match_##SP(const DevModel& d, const Lds& L) { return spec_matches<SP>(d, L); }
+#endif
 #define DX_SPEC_DEFINE(SP)                                                                            \
-  bool dx_match_##SP(const DevModel& d, const Lds& L) { return spec_matches<SP>(d, L); }             \
-  int dx_occ_##SP(size_t lds) {                                                                       \
+  DX_SPEC_MATCH(SP)                                                                                   \
+  int DX_PF(dx_occ, SP)(size_t lds) {                                                                 \
     int n = 0;                                                                                        \
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, dx_step_kernel_queue_spec<SP>, 64, lds) != hipSuccess) n = 0; \
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, DX_PN(dx_step_kernel_queue_spec)<SP>, 64, lds) != hipSuccess) n = 0; \
     return n;                                                                                         \
   }                                                                                                   \
-  hipError_t dx_launch_##SP(int grid, size_t lds, hipStream_t stream, const DevModel* m, const DevBatch& B, \
-                            const Lds& L, int nsub, int mode) {                                       \
+  hipError_t DX_PF(dx_launch, SP)(int grid, size_t lds, hipStream_t stream, const DevModel* m, const DevBatch& B, \
+                                  const Lds& L, int nsub, int mode) {                                 \
     if (mode == 2)                                                                                    \
-      hipLaunchKernelGGL(dx_prep_kernel_spec<SP>, dim3(grid), dim3(64), lds, stream, m, B, L);         \
+      hipLaunchKernelGGL(DX_PN(dx_prep_kernel_spec)<SP>, dim3(grid), dim3(64), lds, stream, m, B, L);  \
     else if (mode == 3)                                                                               \
-      hipLaunchKernelGGL(dx_step_kernel_queue_spec<SP>, dim3(grid), dim3(64), lds, stream, m, B, L, nsub);  \
+      hipLaunchKernelGGL(DX_PN(dx_step_kernel_queue_spec)<SP>, dim3(grid), dim3(64), lds, stream, m, B, L, nsub);  \
     else                                                                                              \
-      hipLaunchKernelGGL(dx_step_kernel_spec<SP>, dim3(grid), dim3(64), lds, stream, m, B, L, nsub, mode); \
+      hipLaunchKernelGGL(DX_PN(dx_step_kernel_spec)<SP>, dim3(grid), dim3(64), lds, stream, m, B, L, nsub, mode); \
     return hipGetLastError();                                                                         \
   }
 #define DX_SPEC_DEFINE1(SP) DX_SPEC_DEFINE(SP)
 DX_SPEC_DEFINE1(DX_SPEC_ONLY)
 #else
-DX_SPECS(DX_SPEC_FNS)
-
 // The model struct is read through a device pointer (dx_batch.hip device_model) in
 // the constant address space rather than passed by value in the kernarg segment.
 extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DX_STEP_WAVES)))
-dx_step_kernel(const DevModel* __restrict__ mp, DevBatch B, Lds L, int nsub, int mode) {
+DX_PN(dx_step_kernel)(const DevModel* __restrict__ mp, DevBatch B, Lds L, int nsub, int mode) {
   const DevModel& m = *(const DevModel*)(const DXG DevModel*)mp;
   if (mode == 3) step_queue<SpecRT>(m, B, L, nsub);
   else step_body<SpecRT>(m, B, L, nsub, mode);
 }
 extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2)))
-dx_prep_kernel(const DevModel* __restrict__ mp, DevBatch B, Lds L) {
+DX_PN(dx_prep_kernel)(const DevModel* __restrict__ mp, DevBatch B, Lds L) {
   const DevModel& m = *(const DevModel*)(const DXG DevModel*)mp;
   step_body<SpecRT>(m, B, L, 1, 2, true);
 }
+// the generic kernels' occupancy and launch (their twins': dx_occ_prof_generic, dx_launch_prof_generic)
+int DX_PF(dx_occ, generic)(size_t lds) {
+  int n = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, DX_PN(dx_step_kernel), 64, lds) != hipSuccess) n = 0;
+  return n;
+}
+hipError_t DX_PF(dx_launch, generic)(int grid, size_t lds, hipStream_t stream, const DevModel* m, const DevBatch& B,
+                                     const Lds& L, int nsub, int mode) {
+  if (mode == 2)
+    hipLaunchKernelGGL(DX_PN(dx_prep_kernel), dim3(grid), dim3(64), lds, stream, m, B, L);
+  else
+    hipLaunchKernelGGL(DX_PN(dx_step_kernel), dim3(grid), dim3(64), lds, stream, m, B, L, nsub, mode);
+  return hipGetLastError();
+}
+#if !DX_PROF  // (the rest of the unit is the production build's alone)
+DX_SPECS(DX_SPEC_FNS)
+int dx_occ_prof_generic(size_t lds);
+hipError_t dx_launch_prof_generic(int grid, size_t lds, hipStream_t stream, const DevModel* m, const DevBatch& B,
+                                  const Lds& L, int nsub, int mode);
 
 // Resident step-kernel workgroups per CU at `lds` bytes of LDS each (0: unknown), for
-// the persistent grid of the substep queue.
-int dx_step_occupancy(int spec, size_t lds) {
+// the persistent grid of the substep queue; `prof`: of the instrumented twin.
+int dx_step_occupancy(int spec, size_t lds, bool prof) {
   int k = 0;
-#define DX_OCC(SP) if (spec == k) return dx_occ_##SP(lds); k++;
+#define DX_OCC(SP) if (spec == k) return prof ? dx_occ_prof_##SP(lds) : dx_occ_##SP(lds); k++;
   DX_SPECS(DX_OCC)
 #undef DX_OCC
   (void)k;
-  int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, dx_step_kernel, 64, lds) != hipSuccess) n = 0;
-  return n;
+  return prof ? dx_occ_prof_generic(lds) : dx_occ_generic(lds);
 }
 
 // Whether specialization `spec` carries the fused reach sampling pass (fused_reach_prep).
@@ -4833,18 +4880,19 @@ hipError_t dx_launch_order(int nenv, hipStream_t stream, const unsigned* cost, i
 
 hipError_t dx_launch_step(int spec, int grid, size_t lds, hipStream_t stream, const DevModel* m, const DevBatch& B,
                           const Lds& L, int nsub, int mode) {
+  // a batch with stage timing on (dx_stage_timing) runs the instrumented twins
+  const bool prof = B.stage_acc != nullptr;
   int k = 0;
-#define DX_LAUNCH(SP)                                                         \
-  if (spec == k) return dx_launch_##SP(grid, lds, stream, m, B, L, nsub, mode); \
+#define DX_LAUNCH(SP)                                                                              \
+  if (spec == k)                                                                                   \
+    return prof ? dx_launch_prof_##SP(grid, lds, stream, m, B, L, nsub, mode)                      \
+                : dx_launch_##SP(grid, lds, stream, m, B, L, nsub, mode);                          \
   k++;
   DX_SPECS(DX_LAUNCH)
 #undef DX_LAUNCH
   (void)k;
-  if (mode == 2)
-    hipLaunchKernelGGL(dx_prep_kernel, dim3(grid), dim3(64), lds, stream, m, B, L);
-  else
-    hipLaunchKernelGGL(dx_step_kernel, dim3(grid), dim3(64), lds, stream, m, B, L, nsub, mode);
-  return hipGetLastError();
+  return prof ? dx_launch_prof_generic(grid, lds, stream, m, B, L, nsub, mode)
+              : dx_launch_generic(grid, lds, stream, m, B, L, nsub, mode);
 }
 
 // reset envs [env0, env0+n) to qpos0
@@ -4863,4 +4911,5 @@ extern "C" __global__ void dx_reset_kernel(DevModel m, DevBatch B, int env0, int
     if (B.nstep) B.nstep[env] = 0;
   }
 }
+#endif  // !DX_PROF
 #endif  // DX_TIER_HI / DX_TIER_MID / DX_SPEC_ONLY
