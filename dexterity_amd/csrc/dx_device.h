@@ -251,6 +251,12 @@ __device__ __forceinline__ float dot6(const float* a, const float* b) {
 struct SpecRT {
   static constexpr bool reach_task = false;  // (the generic kernel: no fused reach sampling pass)
 };
+// The exact line search's register slots, 64 constraint rows each (dx_step.hip line_search).
+// The generic kernel and the tiers: nefc_max <= 320 / 1280, checked at model load.  A scene
+// specialization: its own row bound (CtxT::ls_slots).
+#ifndef DX_LS_SLOTS
+#define DX_LS_SLOTS (DX_NCON_MAX > 64 ? 20 : 5)
+#endif
 // DX_PROF: the per-stage profiler is a compile-time switch.  build.py compiles every
 // dx_step.hip unit twice: the production kernels without it (the context then has no
 // stage_acc member, c.acc() is a constant null, and stage_mark, stage_count, the
@@ -281,6 +287,11 @@ struct CtxT {
 #define DX_X(n) static constexpr int n = SP::n;
   DX_DIMS(DX_X)
 #undef DX_X
+  // (a limited joint or tendon with a range narrower than twice its margin holds two rows,
+  // dx_model.hip lds_layout: then the layout's capacity is above this sum and the assert fires)
+  static constexpr int ls_slots = (nfric + nlimj + nlimt + 4 * DX_NCON_MAX + DX_WAVE - 1) / DX_WAVE;
+  static_assert(ls_slots * DX_WAVE >= L.nefc_max, "the line search's slots hold the layout's row capacity");
+  static_assert(ls_slots <= DX_LS_SLOTS, "the model-load check bounds every layout's rows by DX_LS_SLOTS");
   float* S;
   int* I;  // misc ints
   DX_PROF_MEMBER
@@ -296,6 +307,7 @@ struct CtxT {
 template <>
 struct CtxT<SpecRT> {
   static constexpr bool is_spec = false;
+  static constexpr int ls_slots = DX_LS_SLOTS;
   const DevModel& m;
   const Lds& L;
 #define DX_X(n) int n;

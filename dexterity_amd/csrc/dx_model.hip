@@ -810,8 +810,11 @@ extern "C" dx_model* dx_model_load(const void* blob, size_t nbytes) {
   const bool tiers = !d.disable_contact && d.ngpair > 0;
   m->ncon_max = tiers ? DX_NCON_HI : DX_NCON_MAX;
   m->nefc_max = tiers ? m->lds_hi.nefc_max : m->lds.nefc_max;
-  // line-search register slots (dx_step.hip DX_LS_SLOTS: 5 in the step kernel, 20 in the
-  // overflow tier)
+  // line-search register slots (dx_device.h DX_LS_SLOTS: 5 in the generic step kernel and
+  // the mid tier, 20 in the overflow tier; a scene specialization keeps CtxT::ls_slots, its
+  // own row bound, which a static_assert holds at or below DX_LS_SLOTS).  The literal 5 * 64
+  // here and above (lds_mid) and 20 * 64 must stay in step with DX_LS_SLOTS: that assert and
+  // the kernels' register arrays rely on this check
   if (m->lds.nefc_max > 5 * 64 || (tiers && m->lds_hi.nefc_max > 20 * 64)) {
     dx_fail(DX_ELIMIT, "constraint row capacity exceeds the line search's register slots");
     return nullptr;

@@ -2479,10 +2479,9 @@ __device__ __forceinline__ int row_zone(int type, float Rf, float jar) {
 
 // Exact line search along dir (1-D Newton with bracketing on the piecewise-quadratic
 // cost).  Every row's (type, D, friction, jar, J dir) is loaded into registers once
-// -- lane-owned rows r = LANE + 64 k -- so the iterations touch no LDS.
-#ifndef DX_LS_SLOTS
-#define DX_LS_SLOTS (DX_NCON_MAX > 64 ? 20 : 5)  // nefc_max <= 320 / 1280 (checked at model load)
-#endif
+// -- lane-owned rows r = LANE + 64 k, Ctx::ls_slots of them (dx_device.h DX_LS_SLOTS; three
+// in the reorient specialization, whose 176 rows cannot reach a fourth) -- so the iterations
+// touch no LDS.
 // NEWTON (dir = -H^-1 grad): the slope at alpha = 0 is grad . dir and the curvature there
 // dir^T H dir = -grad . dir (H is the Hessian of the zone set at alpha = 0), so the first
 // 1-D Newton step from 0 lands at alpha = 1 -- the search starts there, with g0 = grad . dir
@@ -2525,10 +2524,11 @@ __device__ __forceinline__ float line_search(const Ctx& c, const float* qacc, co
   const float* flp = c.f(c.L.efc_fl);
   const float* Rfp = c.f(c.L.efc_Rf);
   const float* jarp = c.f(c.L.efc_jar);
-  int ty[DX_LS_SLOTS];
-  float D[DX_LS_SLOTS], fl[DX_LS_SLOTS], Rf[DX_LS_SLOTS], ja[DX_LS_SLOTS], jj[DX_LS_SLOTS];
+  constexpr int NSLOT = Ctx::ls_slots;
+  int ty[NSLOT];
+  float D[NSLOT], fl[NSLOT], Rf[NSLOT], ja[NSLOT], jj[NSLOT];
 #pragma unroll
-  for (int k = 0; k < DX_LS_SLOTS; k++) {
+  for (int k = 0; k < NSLOT; k++) {
     if (k < ns) {  // uniform; the loads read a clamped row and select after (no per-lane branch)
       const int r = LANE + DX_WAVE * k;
       const int rc = max(min(r, nefc - 1), 0);
@@ -2557,7 +2557,7 @@ __device__ __forceinline__ float line_search(const Ctx& c, const float* qacc, co
   for (; it < 40; it++) {
     float g = 0, h = 0;
 #pragma unroll
-    for (int k = 0; k < DX_LS_SLOTS; k++) {
+    for (int k = 0; k < NSLOT; k++) {
       if (k < ns) {
         float f, hw;
         row_force(ty[k], D[k], fl[k], Rf[k], ja[k] + alpha * jj[k], f, hw);
@@ -2582,7 +2582,7 @@ __device__ __forceinline__ float line_search(const Ctx& c, const float* qacc, co
     float* jw = c.f(c.L.efc_jar);
     float rc = 0.f;
 #pragma unroll
-    for (int k = 0; k < DX_LS_SLOTS; k++) {
+    for (int k = 0; k < NSLOT; k++) {
       if (k < ns) {
         const float jn = ja[k] + alpha * jj[k];
         float f, hw;
@@ -2598,7 +2598,7 @@ __device__ __forceinline__ float line_search(const Ctx& c, const float* qacc, co
   // rows whose cost zone differs between the current point and the new one
   int ch = 0;
 #pragma unroll
-  for (int k = 0; k < DX_LS_SLOTS; k++)
+  for (int k = 0; k < NSLOT; k++)
     if (k < ns) ch += jj[k] != 0.f && row_zone(ty[k], Rf[k], ja[k]) != row_zone(ty[k], Rf[k], ja[k] + alpha * jj[k]);
   *changed = wave_sum_i(ch);
   return alpha;
