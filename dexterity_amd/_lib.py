@@ -48,6 +48,7 @@ EXPORTS = (
     "dx_set_xfrc_env", "dx_get_xfrc_env", "dx_xfrc_ptr", "dx_env_set_perturbation", "dx_env_perturb_draw",
     "dx_model_hull_planes", "dx_render_set_cameras", "dx_render", "dx_render_output", "dx_render_get",
     "dx_render_stats", "dx_ray", "dx_env_set_cameras",
+    "dx_render_set_shading", "dx_env_set_shading", "dx_render_stats2",
 )
 COMM_ID_BYTES = 128
 STAGES = ("kinematics", "crb", "broadphase", "midphase", "narrowphase", "constraints", "velocity",
@@ -72,6 +73,9 @@ PERTURB_MAX_BODIES = 4
 OUT_DEPTH, OUT_SEGMENTATION = 13, 14
 RENDER_DEPTH, RENDER_SEGMENTATION, RENDER_NO_CULL = 1, 2, 4  # dx_render_set_cameras flags / dx_render_output
 RENDER_MAX_CAMERAS, RENDER_MAX_SIDE = 8, 512
+OUT_RGB = 15
+RENDER_RGB = 8
+RENDER_MAX_LIGHTS, RENDER_MAX_FACE_GEOMS = 4, 8
 # dx_obs_pipeline.padding / .aggregator, by composer's names
 OBS_PAD = {"zero": 0, "initial_value": 1}
 OBS_AGG = {None: 0, "min": 1, "max": 2, "mean": 3, "median": 4, "sum": 5}
@@ -167,6 +171,59 @@ class Camera(ctypes.Structure):
         ("far_", ctypes.c_float),
         ("body", ctypes.c_int32),
     ]
+
+
+class Light(ctypes.Structure):
+    """struct dx_light (include/dx.h)."""
+
+    _fields_ = [
+        ("pos", ctypes.c_float * 3),
+        ("dir", ctypes.c_float * 3),
+        ("diffuse", ctypes.c_float * 3),
+        ("directional", ctypes.c_int32),
+        ("castshadow", ctypes.c_int32),
+    ]
+
+
+class Shading(ctypes.Structure):
+    """struct dx_shading (include/dx.h)."""
+
+    _fields_ = [
+        ("ambient", ctypes.c_float * 3),
+        ("background", ctypes.c_float * 3),
+        ("headlight", ctypes.c_float * 3),
+        ("checker_rgb", ctypes.c_float * 6),
+        ("checker_cell", ctypes.c_float),
+    ]
+
+
+def shading_args(geom_rgb, face_geom, face_rgb, lights, shading):
+    """The arguments of dx_render_set_shading / dx_env_set_shading behind the handle, from
+    what cameras.validate_shading returns (None: that part's default), and the objects that
+    must stay alive over the call."""
+    nface = 0 if face_geom is None else len(face_geom)
+    fg = None if face_geom is None else (ctypes.c_int32 * max(nface, 1))(*[int(g) for g in face_geom])
+    larr = None
+    if lights is not None:
+        larr = (Light * max(len(lights), 1))()
+        for c, l in zip(larr, lights):
+            c.pos[:] = [float(v) for v in l.pos]
+            c.dir[:] = [float(v) for v in l.dir]
+            c.diffuse[:] = [float(v) for v in l.diffuse]
+            c.directional, c.castshadow = int(bool(l.directional)), int(bool(l.castshadow))
+    sh = None
+    if shading is not None:
+        sh = Shading()
+        sh.ambient[:] = [float(v) for v in shading.ambient]
+        sh.background[:] = [float(v) for v in shading.background]
+        sh.headlight[:] = [float(v) for v in shading.headlight]
+        sh.checker_rgb[:] = [float(v) for row in shading.checker_rgb for v in row]
+        sh.checker_cell = float(shading.checker_cell)
+    keep = (geom_rgb, face_rgb, fg, larr, sh)
+    args = (None if geom_rgb is None else geom_rgb.ctypes.data, fg,
+            None if face_rgb is None or not nface else face_rgb.ctypes.data, nface,
+            larr, 0 if lights is None else len(lights), None if sh is None else ctypes.byref(sh))
+    return args, keep
 
 
 def load(path: str = LIB_PATH):
@@ -281,6 +338,10 @@ def load(path: str = LIB_PATH):
         L.dx_render_stats.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
         L.dx_ray.argtypes = [vp, vp, vp, i32, vp, vp]
         L.dx_env_set_cameras.argtypes = [vp, vp, i32, i32, i32, i32]
+    if hasattr(L, "dx_render_set_shading"):  # (an older variant library for A/B lacks the shaded RGB)
+        L.dx_render_set_shading.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp]
+        L.dx_env_set_shading.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp]
+        L.dx_render_stats2.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.dx_timing_enable.argtypes = [vp, ctypes.c_int]
     L.dx_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i32)]
     L.dx_stage_timing.argtypes = [vp, ctypes.c_int]

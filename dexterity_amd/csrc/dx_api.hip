@@ -641,6 +641,18 @@ extern "C" int dx_env_set_cameras(dx_env* e, const dx_camera* cams, int32_t ncam
   return 0;
 }
 
+// The shading settings of the env's batch; RGB images that are on are rendered afresh.
+extern "C" int dx_env_set_shading(dx_env* e, const float* geom_rgb, const int32_t* face_geom, const float* face_rgb,
+                                  int32_t nface, const dx_light* lights, int32_t nlight, const dx_shading* shading) {
+  if (!e) return dx_fail(DX_EINVAL, "null env");
+  dx_batch* b = e->batch;
+  if (int rc = dx_render_set_shading(b, geom_rgb, face_geom, face_rgb, nface, lights, nlight, shading)) return rc;
+  if (!b->RA.ncam || !(b->rnd_flags & DX_RENDER_RGB)) return 0;
+  if (int rc = dx_render(b)) return rc;
+  HIPCHK(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
 extern "C" int dx_env_hand_obs_dim(const dx_env* e) {
   if (!e) return dx_fail(DX_EINVAL, "null env");
   return e->H.mask ? e->H.dim : 0;
@@ -958,14 +970,19 @@ extern "C" int dx_env_output(dx_env* e, int which, void** devptr) {
       *devptr = e->PT.wrench;
       return 0;
     case DX_OUT_DEPTH:
-      if (!e->batch->RA.ncam || !e->batch->RA.depth)
+      if (!e->batch->RA.ncam || !(e->batch->rnd_flags & DX_RENDER_DEPTH))
         return dx_fail(DX_EINVAL, "no depth images: dx_env_set_cameras has no camera with DX_RENDER_DEPTH on");
       *devptr = e->batch->RA.depth;
       return 0;
     case DX_OUT_SEGMENTATION:
-      if (!e->batch->RA.ncam || !e->batch->RA.seg)
+      if (!e->batch->RA.ncam || !(e->batch->rnd_flags & DX_RENDER_SEGMENTATION))
         return dx_fail(DX_EINVAL, "no segmentation images: dx_env_set_cameras has no camera with DX_RENDER_SEGMENTATION on");
       *devptr = e->batch->RA.seg;
+      return 0;
+    case DX_OUT_RGB:
+      if (!e->batch->RA.ncam || !(e->batch->rnd_flags & DX_RENDER_RGB))
+        return dx_fail(DX_EINVAL, "no RGB images: dx_env_set_cameras has no camera with DX_RENDER_RGB on");
+      *devptr = e->batch->rnd_rgb;
       return 0;
   }
   return dx_fail(DX_EINVAL, "unknown output");

@@ -98,8 +98,17 @@ struct dx_batch {
   int* rnd_seg = nullptr;
   size_t rnd_depth_cap = 0, rnd_seg_cap = 0;
   int rnd_prev_bodies = -1;
-  unsigned long long* rnd_stats = nullptr;
+  unsigned long long* rnd_stats = nullptr;  // the cast's triple, then the shadow cull's
   bool rnd_stats_on = false;
+  // shaded RGB (DX_RENDER_RGB): RA.depth / RA.seg are then always set -- the cast writes them
+  // for the shading pass -- and rnd_flags says which of them the caller asked for.  The
+  // settings (dx_render_set_shading) persist across camera configurations; shade_tab is
+  // [ngeom][3] geom colours followed by the face colours, allocated by the first use.
+  unsigned char* rnd_rgb = nullptr;
+  size_t rnd_rgb_cap = 0;  // in words
+  ShadeSet shade{};
+  bool shade_set = false;  // (false: the documented defaults, filled in at first use)
+  float* shade_tab = nullptr;
 };
 
 // Per-call device scratch, released (after the batch stream drains) on every exit path.
@@ -159,8 +168,7 @@ extern std::recursive_mutex g_render_mu;  // the plane table and its per-device 
 double dx_getd(const dx_model* m, const char* name, double def = 0);
 int hull_planes(dx_model* m);
 int balloc(dx_batch* b, void** p, size_t bytes);
-int render_tables(dx_model* m, int device, dx_model::RenderDev* out);
-int queue_check(dx_batch* b);
+int render_tables(dx_model* m, int device, dx_model::RenderDev* out);int queue_check(dx_batch* b);
 int xfrc_env_mode(dx_batch* b);
 int launch_sensor(dx_batch* b, const ContactSense* env_pads, float* env_out);
 int launch_step(dx_batch* b, int nsub, int mode);

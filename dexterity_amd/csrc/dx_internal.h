@@ -608,6 +608,30 @@ struct RenderArgs {
 };
 hipError_t dx_launch_render(hipStream_t stream, const RenderArgs& A);
 hipError_t dx_launch_rays(hipStream_t stream, const RenderArgs& A);
+// The shading pass (dx_render.hip dx_shade_kernel), launched behind dx_render_kernel: it
+// reads that kernel's depth and segmentation images and writes the RGB bytes.
+#define DX_SHADE_REC 28       // a shadow-list record: the cast's 24 words and the light in the geom frame
+struct ShadeLight {
+  float v[3];                 // directional: the unit vector towards the light; else its position
+  float diffuse[3];
+  int directional, castshadow;
+};
+struct ShadeSet {             // the settings (dx_render_set_shading), kept by the batch
+  int nlight, nface;
+  ShadeLight light[DX_RENDER_MAX_LIGHTS];
+  int face_geom[DX_RENDER_MAX_FACE_GEOMS];
+  float ambient[3], background[3], headlight[3];
+  float checker_rgb[2][3], checker_cell;
+  int headlight_on;
+};
+struct ShadeArgs {
+  RenderArgs R;               // depth and seg: the cast's images (never null here)
+  ShadeSet S;
+  const float* geom_rgb;      // [ngeom][3], then the face colours [DX_RENDER_MAX_FACE_GEOMS][6][3]
+  unsigned char* rgb;         // [nenv][ncam][H][W][3]
+  unsigned long long* stats;  // the shadow cull's triple, or null
+};
+hipError_t dx_launch_shade(hipStream_t stream, const ShadeArgs& A);
 
 // dx_perturb.hip: the random pushes, queued ahead of the step's launches, and their test hook
 hipError_t dx_launch_perturb(hipStream_t stream, const Perturb& P);

@@ -326,9 +326,10 @@ extern "C" int dx_render_set_cameras(dx_batch* b, const dx_camera* cams, int32_t
   }
   if (!cams || ncam < 0) return dx_fail(DX_EINVAL, "cameras: null camera array or negative count");
   if (width < 1 || height < 1) return dx_fail(DX_EINVAL, "cameras: width and height must be positive");
-  if (flags & ~(DX_RENDER_DEPTH | DX_RENDER_SEGMENTATION | DX_RENDER_NO_CULL)) return dx_fail(DX_EINVAL, "cameras: unknown flag");
-  if (!(flags & (DX_RENDER_DEPTH | DX_RENDER_SEGMENTATION)))
-    return dx_fail(DX_EINVAL, "cameras: no output flag (DX_RENDER_DEPTH / DX_RENDER_SEGMENTATION)");
+  if (flags & ~(DX_RENDER_DEPTH | DX_RENDER_SEGMENTATION | DX_RENDER_NO_CULL | DX_RENDER_RGB))
+    return dx_fail(DX_EINVAL, "cameras: unknown flag");
+  if (!(flags & (DX_RENDER_DEPTH | DX_RENDER_SEGMENTATION | DX_RENDER_RGB)))
+    return dx_fail(DX_EINVAL, "cameras: no output flag (DX_RENDER_DEPTH / DX_RENDER_SEGMENTATION / DX_RENDER_RGB)");
   if (ncam > DX_RENDER_MAX_CAMERAS) return dx_fail(DX_ELIMIT, "cameras: more than 8 cameras");
   if (width > DX_RENDER_MAX_SIDE || height > DX_RENDER_MAX_SIDE) return dx_fail(DX_ELIMIT, "cameras: a side above 512 pixels");
   const unsigned long long npix = (unsigned long long)b->nenv * ncam * height * width;
@@ -345,29 +346,36 @@ extern "C" int dx_render_set_cameras(dx_batch* b, const dx_camera* cams, int32_t
     if (!camera_frame(c, A.cam[i], height)) return dx_fail(DX_EINVAL, "cameras: degenerate xyaxes");
   }
   if (int rc = render_base(b, A)) return rc;
-  void *nd = b->rnd_depth, *ns = b->rnd_seg;
-  bool fd = false, fs = false;
-  if (flags & DX_RENDER_DEPTH)
-    if (int rc = render_buffer(b, b->rnd_depth, b->rnd_depth_cap, (size_t)npix, &nd, &fd)) return rc;
-  if (flags & DX_RENDER_SEGMENTATION)
-    if (int rc = render_buffer(b, b->rnd_seg, b->rnd_seg_cap, (size_t)npix, &ns, &fs)) {
-      if (fd) (void)hipFree(nd);
-      return rc;
-    }
-  if (hipStreamSynchronize(b->stream) != hipSuccess) {
+  // the shading pass reads the cast's depth and geom ids: with RGB on the cast writes both,
+  // into the same buffers, whether or not the caller asked for them (rnd_flags says which)
+  const bool rgb = (flags & DX_RENDER_RGB) != 0;
+  const bool want_d = rgb || (flags & DX_RENDER_DEPTH), want_s = rgb || (flags & DX_RENDER_SEGMENTATION);
+  if (rgb && !b->shade_set)  // the documented default shading
+    if (int rc = dx_render_set_shading(b, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr)) return rc;
+  const size_t rgb_words = (size_t)((npix * 3 + 3) / 4);
+  void *nd = b->rnd_depth, *ns = b->rnd_seg, *nc = b->rnd_rgb;
+  bool fd = false, fs = false, fc = false;
+  int rc = 0;
+  if (want_d) rc = render_buffer(b, b->rnd_depth, b->rnd_depth_cap, (size_t)npix, &nd, &fd);
+  if (!rc && want_s) rc = render_buffer(b, b->rnd_seg, b->rnd_seg_cap, (size_t)npix, &ns, &fs);
+  if (!rc && rgb) rc = render_buffer(b, b->rnd_rgb, b->rnd_rgb_cap, rgb_words, &nc, &fc);
+  if (!rc && hipStreamSynchronize(b->stream) != hipSuccess) rc = dx_fail(DX_EHIP, "cameras: stream sync failed");
+  if (rc) {
     if (fd) (void)hipFree(nd);
     if (fs) (void)hipFree(ns);
-    return dx_fail(DX_EHIP, "cameras: stream sync failed");
+    if (fc) (void)hipFree(nc);
+    return rc;
   }
   // every step has succeeded: the new buffers replace the old ones
   if (fd) render_adopt(b, (void**)&b->rnd_depth, &b->rnd_depth_cap, nd, (size_t)npix);
   if (fs) render_adopt(b, (void**)&b->rnd_seg, &b->rnd_seg_cap, ns, (size_t)npix);
+  if (fc) render_adopt(b, (void**)&b->rnd_rgb, &b->rnd_rgb_cap, nc, rgb_words);
   A.ncam = ncam; A.W = width; A.H = height;
   A.tiles_x = (width + DX_RENDER_TILE - 1) / DX_RENDER_TILE;
   A.tiles_y = (height + DX_RENDER_TILE - 1) / DX_RENDER_TILE;
   A.no_cull = (flags & DX_RENDER_NO_CULL) ? 1 : 0;
-  A.depth = (flags & DX_RENDER_DEPTH) ? b->rnd_depth : nullptr;
-  A.seg = (flags & DX_RENDER_SEGMENTATION) ? b->rnd_seg : nullptr;
+  A.depth = want_d ? b->rnd_depth : nullptr;
+  A.seg = want_s ? b->rnd_seg : nullptr;
   b->RA = A;
   b->rnd_flags = flags;
   if (b->rnd_prev_bodies < 0) b->rnd_prev_bodies = b->db.out_bodies;
@@ -382,15 +390,150 @@ extern "C" int dx_render(dx_batch* b) {
   RenderArgs A = b->RA;
   A.stats = b->rnd_stats_on ? b->rnd_stats : nullptr;
   HIPCHK(dx_launch_render(b->stream, A));
+  if (b->rnd_flags & DX_RENDER_RGB) {  // the shading pass, over the images the cast just wrote
+    ShadeArgs S{};
+    S.R = A;
+    S.S = b->shade;
+    S.geom_rgb = b->shade_tab;
+    S.rgb = b->rnd_rgb;
+    S.stats = A.stats ? A.stats + 3 : nullptr;
+    HIPCHK(dx_launch_shade(b->stream, S));
+  }
   return 0;
 }
 
 extern "C" int dx_render_output(dx_batch* b, int which, void** devptr) {
   if (!b || !devptr) return dx_fail(DX_EINVAL, "null argument");
   if (!b->RA.ncam) return dx_fail(DX_EINVAL, "render: no cameras (dx_render_set_cameras)");
-  if (which == DX_RENDER_DEPTH && b->RA.depth) { *devptr = b->RA.depth; return 0; }
-  if (which == DX_RENDER_SEGMENTATION && b->RA.seg) { *devptr = b->RA.seg; return 0; }
+  // (with RGB on the cast's buffers exist without having been asked for: the flags decide)
+  if (which == DX_RENDER_DEPTH && (b->rnd_flags & DX_RENDER_DEPTH)) { *devptr = b->RA.depth; return 0; }
+  if (which == DX_RENDER_SEGMENTATION && (b->rnd_flags & DX_RENDER_SEGMENTATION)) { *devptr = b->RA.seg; return 0; }
+  if (which == DX_RENDER_RGB && (b->rnd_flags & DX_RENDER_RGB)) { *devptr = b->rnd_rgb; return 0; }
   return dx_fail(DX_EINVAL, "render: that output is not enabled");
+}
+
+// The documented default palette (dexterity_amd/cameras.py default_palette mirrors it): the
+// world's geoms one colour, each hand's -- a tree whose root has no free joint, in root order --
+// one of two, a free-jointed prop's geoms one, and the first such box six face colours.
+static const float kPaletteWorld[3] = {0.45f, 0.45f, 0.5f}, kPaletteProp[3] = {0.8f, 0.8f, 0.8f};
+static const float kPaletteHands[2][3] = {{0.85f, 0.65f, 0.5f}, {0.5f, 0.65f, 0.85f}};
+static const float kPaletteFaces[6][3] = {{0.9f, 0.1f, 0.1f}, {0.1f, 0.8f, 0.1f}, {0.1f, 0.2f, 0.9f},
+                                          {0.9f, 0.8f, 0.1f}, {0.9f, 0.1f, 0.9f}, {0.1f, 0.8f, 0.8f}};
+static void default_palette(const dx_model* m, std::vector<float>& rgb, int* face_geom) {
+  const auto& gb = m->hi.at("geom_bodyid");
+  const auto& gt = m->hi.at("geom_type");
+  const auto& root = m->hi.at("body_rootid");
+  const auto& jt = m->hi.at("jnt_type");
+  const auto& jb = m->hi.at("jnt_bodyid");
+  std::vector<int> free_root(root.size(), 0), hands;
+  for (size_t j = 0; j < jt.size(); j++)
+    if (jt[j] == 0) free_root[root[jb[j]]] = 1;
+  *face_geom = -1;
+  rgb.assign(gb.size() * 3, 0.f);
+  for (size_t g = 0; g < gb.size(); g++) {
+    const int r = root[gb[g]];
+    const float* c = kPaletteWorld;
+    if (gb[g] != 0 && free_root[r]) {
+      c = kPaletteProp;
+      if (gt[g] == DXG_BOX && *face_geom < 0) *face_geom = (int)g;
+    } else if (gb[g] != 0) {
+      auto it = std::find(hands.begin(), hands.end(), r);
+      if (it == hands.end()) it = hands.insert(hands.end(), r);
+      c = kPaletteHands[(it - hands.begin()) % 2];
+    }
+    for (int k = 0; k < 3; k++) rgb[3 * g + k] = c[k];
+  }
+}
+
+static bool finite_all(const float* v, size_t n) {
+  for (size_t i = 0; i < n; i++)
+    if (!std::isfinite(v[i])) return false;
+  return true;
+}
+
+extern "C" int dx_render_set_shading(dx_batch* b, const float* geom_rgb, const int32_t* face_geom, const float* face_rgb,
+                                     int32_t nface, const dx_light* lights, int32_t nlight, const dx_shading* shading) {
+  if (!b) return dx_fail(DX_EINVAL, "null batch");
+  const dx_model* m = b->model;
+  const int ngeom = b->dm.ngeom;
+  if (nface < 0 || nlight < 0) return dx_fail(DX_EINVAL, "shading: a negative count");
+  if (nface > DX_RENDER_MAX_FACE_GEOMS) return dx_fail(DX_ELIMIT, "shading: more than 8 face geoms");
+  if (nlight > DX_RENDER_MAX_LIGHTS) return dx_fail(DX_ELIMIT, "shading: more than 4 lights");
+  if ((nface && (!face_geom || !face_rgb)) || (nlight && !lights))
+    return dx_fail(DX_EINVAL, "shading: a null array with a positive count");
+  ShadeSet S{};
+  std::vector<float> tab;
+  int def_face = -1;
+  default_palette(m, tab, &def_face);
+  if (geom_rgb) {
+    if (!finite_all(geom_rgb, (size_t)ngeom * 3)) return dx_fail(DX_EINVAL, "shading: a non-finite geom colour");
+    std::copy(geom_rgb, geom_rgb + (size_t)ngeom * 3, tab.begin());
+  }
+  tab.resize((size_t)ngeom * 3 + DX_RENDER_MAX_FACE_GEOMS * 18, 0.f);
+  float* faces = tab.data() + (size_t)ngeom * 3;
+  if (!geom_rgb && !face_geom && def_face >= 0) {  // the default palette's prop box
+    S.nface = 1;
+    S.face_geom[0] = def_face;
+    std::copy(&kPaletteFaces[0][0], &kPaletteFaces[0][0] + 18, faces);
+  } else {
+    const auto& gt = m->hi.at("geom_type");
+    for (int i = 0; i < nface; i++) {
+      if (face_geom[i] < 0 || face_geom[i] >= ngeom || gt[face_geom[i]] != DXG_BOX)
+        return dx_fail(DX_EINVAL, "shading: a face geom that is not a box geom");
+      for (int j = 0; j < i; j++)
+        if (face_geom[j] == face_geom[i]) return dx_fail(DX_EINVAL, "shading: a repeated face geom");
+      S.face_geom[i] = face_geom[i];
+    }
+    if (nface && !finite_all(face_rgb, (size_t)nface * 18)) return dx_fail(DX_EINVAL, "shading: a non-finite face colour");
+    if (nface) std::copy(face_rgb, face_rgb + (size_t)nface * 18, faces);
+    S.nface = nface;
+  }
+  if (!lights) {  // the arena's light: directional, straight down, casting shadows
+    S.nlight = 1;
+    S.light[0] = ShadeLight{{0.f, 0.f, 1.f}, {0.5f, 0.5f, 0.5f}, 1, 1};
+  } else {
+    S.nlight = nlight;
+    for (int i = 0; i < nlight; i++) {
+      const dx_light& l = lights[i];
+      if (!finite_all(l.pos, 3) || !finite_all(l.dir, 3) || !finite_all(l.diffuse, 3))
+        return dx_fail(DX_EINVAL, "shading: a non-finite light");
+      ShadeLight& o = S.light[i];
+      o.directional = l.directional != 0;
+      o.castshadow = l.castshadow != 0;
+      for (int k = 0; k < 3; k++) o.diffuse[k] = l.diffuse[k];
+      if (o.directional) {
+        const double d[3] = {l.dir[0], l.dir[1], l.dir[2]};
+        const double n = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+        if (!(n > 0.0)) return dx_fail(DX_EINVAL, "shading: a directional light with a zero dir");
+        for (int k = 0; k < 3; k++) o.v[k] = (float)(-d[k] / n);
+      } else {
+        for (int k = 0; k < 3; k++) o.v[k] = l.pos[k];
+      }
+    }
+  }
+  if (!shading) {
+    for (int k = 0; k < 3; k++) { S.ambient[k] = 0.2f; S.background[k] = 0.f; S.headlight[k] = 0.3f; }
+  } else {
+    if (!finite_all(shading->ambient, 3) || !finite_all(shading->background, 3) || !finite_all(shading->headlight, 3) ||
+        !finite_all(&shading->checker_rgb[0][0], 6) || !finite_all(&shading->checker_cell, 1))
+      return dx_fail(DX_EINVAL, "shading: a non-finite value");
+    if (shading->checker_cell < 0.f) return dx_fail(DX_EINVAL, "shading: a negative checker_cell");
+    for (int k = 0; k < 3; k++) {
+      S.ambient[k] = shading->ambient[k]; S.background[k] = shading->background[k]; S.headlight[k] = shading->headlight[k];
+      S.checker_rgb[0][k] = shading->checker_rgb[0][k]; S.checker_rgb[1][k] = shading->checker_rgb[1][k];
+    }
+    S.checker_cell = shading->checker_cell;
+  }
+  S.headlight_on = S.headlight[0] != 0.f || S.headlight[1] != 0.f || S.headlight[2] != 0.f;
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));  // may be called between renders
+  if (!b->shade_tab)
+    if (int rc = balloc(b, (void**)&b->shade_tab, tab.size() * 4)) return rc;
+  HIPCHK(hipStreamSynchronize(b->stream));  // (balloc clears on the stream)
+  HIPCHK(hipMemcpy(b->shade_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+  b->shade = S;
+  b->shade_set = true;
+  return 0;
 }
 
 extern "C" int dx_render_get(dx_batch* b, int which, void* dst_host, int32_t env0, int32_t n) {
@@ -398,7 +541,7 @@ extern "C" int dx_render_get(dx_batch* b, int which, void* dst_host, int32_t env
   if (int rc = dx_render_output(b, which, &src)) return rc;
   if (!dst_host || env0 < 0 || n < 0 || env0 + n > b->nenv) return dx_fail(DX_EINVAL, "render: bad env range or null destination");
   HIPCHK(hipSetDevice(b->device));
-  const size_t per = (size_t)b->RA.ncam * b->RA.H * b->RA.W * 4;
+  const size_t per = (size_t)b->RA.ncam * b->RA.H * b->RA.W * (which == DX_RENDER_RGB ? 3 : 4);
   HIPCHK(hipMemcpyAsync(dst_host, (const char*)src + per * env0, per * n, hipMemcpyDeviceToHost, b->stream));
   HIPCHK(hipStreamSynchronize(b->stream));
   return 0;
@@ -409,11 +552,22 @@ extern "C" int dx_render_stats(dx_batch* b, int enable, uint64_t out[3]) {
   HIPCHK(hipSetDevice(b->device));
   HIPCHK(hipStreamSynchronize(b->stream));
   if (!b->rnd_stats)
-    if (int rc = balloc(b, (void**)&b->rnd_stats, 3 * 8)) return rc;
+    if (int rc = balloc(b, (void**)&b->rnd_stats, 6 * 8)) return rc;
   HIPCHK(hipStreamSynchronize(b->stream));
   if (out) HIPCHK(hipMemcpy(out, b->rnd_stats, 3 * 8, hipMemcpyDeviceToHost));
   HIPCHK(hipMemset(b->rnd_stats, 0, 3 * 8));
   b->rnd_stats_on = enable != 0;
+  return 0;
+}
+
+// the shadow cull's triple (words 3-5 of the same buffer; dx_render_stats switches the counting)
+extern "C" int dx_render_stats2(dx_batch* b, uint64_t out[3]) {
+  if (!b) return dx_fail(DX_EINVAL, "null batch");
+  if (!b->rnd_stats) return dx_fail(DX_EINVAL, "render: the statistics were never enabled (dx_render_stats)");
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  if (out) HIPCHK(hipMemcpy(out, b->rnd_stats + 3, 3 * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemset(b->rnd_stats + 3, 0, 3 * 8));
   return 0;
 }
 

@@ -31,6 +31,9 @@
 //
 // dx_ray runs the same stage two over caller-given rays (one lane per ray, every geom in
 // the list; a record then carries the geom's world pose and the lane rotates its own ray).
+//
+// dx_shade_kernel (below, DX_RENDER_RGB) shades the cast's images in a second launch: normals,
+// lights, shadows through the same entry tests, per-face colours, uint8 RGB.
 #include "../../include/dx.h"
 #include "dx_device.h"
 
@@ -372,6 +375,301 @@ extern "C" __global__ void __launch_bounds__(DX_RENDER_THREADS) dx_ray_kernel(Re
     A.ray_dist[at] = bestg >= 0 ? best : -1.0f;
     A.ray_geom[at] = bestg;
   }
+}
+
+// ---- the shading pass (DX_RENDER_RGB; the model is stated in include/dx.h "Shaded RGB") ----
+// Launched behind dx_render_kernel with the same grid and the same lane-to-pixel map.  A lane
+// reads its pixel's depth t and geom g from the cast's images and rebuilds the hit point the
+// way the cast built the ray: in g's frame, p = o + t d with o and d from the camera moved
+// into that frame.  The normal comes from p alone (per lane: every lane has its own geom, so
+// the hull arg-max loads its planes per lane).
+//  Shadow pass, once per shadow-casting light: the lanes that face the light reduce their hit
+//   points to a bounding sphere (wave shuffles, then LDS).  Stage one culls one geom per lane
+//   against that sphere swept towards the light -- along a ray for a directional light, along
+//   the segment to a positional one: the distance of the geom's inflated bounding sphere to
+//   the ray / segment against the summed radii, which keeps every geom a lane's own test could
+//   accept -- and ballot-compacts the survivors into the LDS list, in geom order.  A record is
+//   the cast's (the camera in the geom frame, so a lane's hit point there is o + t d again)
+//   plus the light in the geom frame.  Stage two walks the list with a wave-uniform trip
+//   count through the cast's own geom_entry: hull plane addresses stay wave-uniform.
+//  Stores go through an LDS tile of bytes: a row's 16 pixels leave as 48 contiguous bytes in
+//   whole dwords (single bytes only where an image row is not dword aligned at its ends).
+// Exactness: as the cast's.  A lane's verdict is masked by its own gate and the cull is
+// conservative, so the bytes are a function of (env, camera, pixel, settings) alone.
+enum { SR_LIGHT = 24 };  // a shadow record's words beyond the cast's (DX_SHADE_REC = 28)
+
+// the unit normal in the geom frame at the surface point p of geom g, and the box face
+__device__ __forceinline__ void surface_normal(const RenderArgs& A, int g, int type, const float* p, float* n, int* face) {
+  const float s0 = A.geom_size[3 * g], s1 = A.geom_size[3 * g + 1], s2 = A.geom_size[3 * g + 2];
+  n[0] = 0.f; n[1] = 0.f; n[2] = 1.f;  // (the plane's)
+  *face = 0;
+  if (type == DXG_SPHERE) {
+    const float inv = 1.0f / sqrtf(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
+    n[0] = p[0] * inv; n[1] = p[1] * inv; n[2] = p[2] * inv;
+  } else if (type == DXG_CAPSULE) {
+    const float qz = p[2] - fminf(fmaxf(p[2], -s1), s1);
+    const float inv = 1.0f / sqrtf(p[0] * p[0] + p[1] * p[1] + qz * qz);
+    n[0] = p[0] * inv; n[1] = p[1] * inv; n[2] = qz * inv;
+  } else if (type == DXG_BOX) {
+    const float e0 = fabsf(p[0]) - s0, e1 = fabsf(p[1]) - s1, e2 = fabsf(p[2]) - s2;
+    int k = e1 > e0 ? 1 : 0;
+    k = e2 > fmaxf(e0, e1) ? 2 : k;
+    const float pk = k == 0 ? p[0] : (k == 1 ? p[1] : p[2]);
+    const float sg = pk < 0.f ? -1.f : 1.f;
+    n[0] = k == 0 ? sg : 0.f; n[1] = k == 1 ? sg : 0.f; n[2] = k == 2 ? sg : 0.f;
+    *face = 2 * k + (pk < 0.f ? 1 : 0);
+  } else if (type == DXG_MESH) {
+    const int mesh = A.geom_dataid[g];
+    const int adr = mesh >= 0 ? A.mesh_planeadr[mesh] : 0, num = mesh >= 0 ? A.mesh_planenum[mesh] : 0;
+    float bv = -RINF;
+    for (int i = 0; i < num; i++) {  // (per-lane loads; straight-line selects)
+      const float4 q = A.plane4[adr + i];
+      const float v = q.x * p[0] + q.y * p[1] + q.z * p[2] + q.w;
+      const bool up = v > bv;
+      bv = up ? v : bv;
+      n[0] = up ? q.x : n[0]; n[1] = up ? q.y : n[1]; n[2] = up ? q.z : n[2];
+    }
+  }
+}
+
+__device__ __forceinline__ float wave_min(float v) {
+  for (int m = 32; m >= 1; m >>= 1) v = fminf(v, __shfl_xor(v, m, 64));
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+  for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
+  return v;
+}
+
+__device__ __forceinline__ int colour_byte(float c) {
+  return (int)fminf(fmaxf(floorf(255.0f * c + 0.5f), 0.f), 255.f);
+}
+
+extern "C" __global__ void __launch_bounds__(DX_RENDER_THREADS) dx_shade_kernel(ShadeArgs SA) {
+  __shared__ float rec[DX_RENDER_CHUNK * DX_SHADE_REC];
+  __shared__ int wcnt[DX_RENDER_THREADS / 64];
+  __shared__ float wbox[DX_RENDER_THREADS / 64][6];
+  __shared__ unsigned char trgb[DX_RENDER_TILE * DX_RENDER_TILE * 3];
+  const RenderArgs& A = SA.R;
+  const ShadeSet& S = SA.S;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int ntile = A.tiles_x * A.tiles_y;
+  const int tile = blockIdx.x % ntile, ec = blockIdx.x / ntile;
+  const int cam = ec % A.ncam, env = ec / A.ncam;
+  const int tx0 = (tile % A.tiles_x) * DX_RENDER_TILE, ty0 = (tile / A.tiles_x) * DX_RENDER_TILE;
+  const RenderCam& C = A.cam[cam];
+
+  // the camera in the world (workgroup-uniform), as the cast builds it
+  float co[3], cx[3], cy[3], cz[3];
+  {
+    float xp[3] = {0.f, 0.f, 0.f}, xq[4] = {1.f, 0.f, 0.f, 0.f}, Rb[9], t[3];
+    if (C.body > 0) {
+      const float* bp = A.xpos + ((size_t)env * A.nbody + C.body) * 3;
+      const float* bq = A.xquat + ((size_t)env * A.nbody + C.body) * 4;
+      xp[0] = bp[0]; xp[1] = bp[1]; xp[2] = bp[2];
+      xq[0] = bq[0]; xq[1] = bq[1]; xq[2] = bq[2]; xq[3] = bq[3];
+    }
+    quat2mat(Rb, xq);
+    matvec3(t, Rb, C.pos);
+    co[0] = xp[0] + t[0]; co[1] = xp[1] + t[1]; co[2] = xp[2] + t[2];
+    matvec3(cx, Rb, C.x);
+    matvec3(cy, Rb, C.y);
+    matvec3(cz, Rb, C.z);
+  }
+  const float inv_f = 1.0f / C.f, hw = 0.5f * (float)A.W, hh = 0.5f * (float)A.H;
+  const int lx = (w & 1) * 8 + (lane & 7), ly = (w >> 1) * 8 + (lane >> 3);
+  const int px = tx0 + lx, py = ty0 + ly;
+  const float u = ((float)px + 0.5f - hw) * inv_f, v = ((float)py + 0.5f - hh) * inv_f;
+  const bool wave_on = tx0 + (w & 1) * 8 < A.W && ty0 + (w >> 1) * 8 < A.H;
+  const bool in_img = px < A.W && py < A.H;
+
+  // the cast's answer for this pixel
+  int g = -1;
+  float t = 0.f;
+  if (in_img) {
+    const size_t at = (((size_t)env * A.ncam + cam) * A.H + py) * A.W + px;
+    g = A.seg[at];
+    t = A.depth[at];
+  }
+  const bool hit = g >= 0 && g < A.ngeom;
+  const int gi = hit ? g : 0;
+  const int type = A.geom_type[gi];
+
+  // the hit point in the geom frame, the normal there, both in the world
+  float p[3], nw[3], P[3];
+  int face;
+  {
+    float gp[3], gR[9], ol[3], ax[3], ay[3], az[3], nl[3];
+    geom_pose(A, env, gi, gp, gR);
+    const float d0[3] = {co[0] - gp[0], co[1] - gp[1], co[2] - gp[2]};
+    mattvec3(ol, gR, d0);
+    mattvec3(ax, gR, cx);
+    mattvec3(ay, gR, cy);
+    mattvec3(az, gR, cz);
+    for (int k = 0; k < 3; k++) p[k] = ol[k] + t * (ax[k] * u - ay[k] * v - az[k]);
+    surface_normal(A, gi, type, p, nl, &face);
+    matvec3(nw, gR, nl);
+    for (int k = 0; k < 3; k++) P[k] = co[k] + t * (cx[k] * u - cy[k] * v - cz[k]);
+  }
+
+  // irradiance: ambient, the headlight (along the camera's +z, no shadow), the lights
+  float E[3] = {S.ambient[0], S.ambient[1], S.ambient[2]};
+  if (S.headlight_on) {
+    const float ndl = fmaxf(nw[0] * cz[0] + nw[1] * cz[1] + nw[2] * cz[2], 0.f);
+    for (int k = 0; k < 3; k++) E[k] += S.headlight[k] * ndl;
+  }
+  int survivors = 0, passes = 0;
+  for (int li = 0; li < S.nlight; li++) {
+    const ShadeLight& L = S.light[li];
+    float lw[3] = {L.v[0], L.v[1], L.v[2]};
+    if (!L.directional) {
+      const float dv[3] = {L.v[0] - P[0], L.v[1] - P[1], L.v[2] - P[2]};
+      const float inv = 1.0f / sqrtf(dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2]);
+      lw[0] = dv[0] * inv; lw[1] = dv[1] * inv; lw[2] = dv[2] * inv;
+    }
+    const float ndl = nw[0] * lw[0] + nw[1] * lw[1] + nw[2] * lw[2];
+    bool occl = false;
+    if (L.castshadow) {  // (workgroup-uniform)
+      const bool need = hit && ndl > 0.f;
+      // the bounding box of the hit points that face the light
+      float lo[3], hi[3];
+      for (int k = 0; k < 3; k++) {
+        lo[k] = wave_min(need ? P[k] : RINF);
+        hi[k] = wave_max(need ? P[k] : -RINF);
+      }
+      if (lane == 0)
+        for (int k = 0; k < 3; k++) { wbox[w][k] = lo[k]; wbox[w][3 + k] = hi[k]; }
+      __syncthreads();
+      for (int k = 0; k < 3; k++) {
+        lo[k] = fminf(fminf(wbox[0][k], wbox[1][k]), fminf(wbox[2][k], wbox[3][k]));
+        hi[k] = fmaxf(fmaxf(wbox[0][3 + k], wbox[1][3 + k]), fmaxf(wbox[2][3 + k], wbox[3][3 + k]));
+      }
+      __syncthreads();  // wbox is the next light's too
+      if (lo[0] <= hi[0]) {  // some lane needs a verdict (workgroup-uniform)
+        passes++;
+        const float bcn[3] = {0.5f * (lo[0] + hi[0]), 0.5f * (lo[1] + hi[1]), 0.5f * (lo[2] + hi[2])};
+        const float ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];
+        const float Rt = 0.5f * sqrtf(ex * ex + ey * ey + ez * ez) * 1.001f + 1e-5f;
+        // the sweep's far end relative to the sphere's centre (positional), its length
+        const float sv[3] = {L.v[0] - bcn[0], L.v[1] - bcn[1], L.v[2] - bcn[2]};
+        const float sl2 = sv[0] * sv[0] + sv[1] * sv[1] + sv[2] * sv[2];
+        for (int base = 0; base < A.ngeom; base += DX_RENDER_CHUNK) {
+          // stage one
+          const int gg = base + tid;
+          bool keep = false;
+          int gtype = -1;
+          float gp[3], gR[9];
+          if (gg < A.ngeom) {
+            gtype = A.geom_type[gg];
+            geom_pose(A, env, gg, gp, gR);
+            keep = true;
+            if (!A.no_cull && gtype != DXG_PLANE) {
+              const float bc[3] = {A.geom_bsphere[4 * gg], A.geom_bsphere[4 * gg + 1], A.geom_bsphere[4 * gg + 2]};
+              float tb[3];
+              matvec3(tb, gR, bc);
+              const float vx = gp[0] + tb[0] - bcn[0], vy = gp[1] + tb[1] - bcn[1], vz = gp[2] + tb[2] - bcn[2];
+              const float v2 = vx * vx + vy * vy + vz * vz;
+              // the parameter of the closest point of the ray (tau >= 0) / segment (0..1)
+              float s;
+              if (L.directional)
+                s = fmaxf(vx * lw[0] + vy * lw[1] + vz * lw[2], 0.f);
+              else
+                s = sl2 > 0.f ? fminf(fmaxf((vx * sv[0] + vy * sv[1] + vz * sv[2]) / sl2, 0.f), 1.f) : 0.f;
+              const float ax_[3] = {L.directional ? lw[0] : sv[0], L.directional ? lw[1] : sv[1], L.directional ? lw[2] : sv[2]};
+              const float qx = vx - s * ax_[0], qy = vy - s * ax_[1], qz = vz - s * ax_[2];
+              const float dist = sqrtf(qx * qx + qy * qy + qz * qz);
+              const float rc = A.geom_bsphere[4 * gg + 3] * 1.002f + 2e-4f + 1e-5f * sqrtf(v2);
+              keep = dist <= Rt + rc;
+            }
+          }
+          int total;
+          const int slot = compact(keep, wcnt, &total);
+          if (keep) {
+            float* r = rec + slot * DX_SHADE_REC;
+            record_head(A, gg, gtype, r);
+            const float d0[3] = {co[0] - gp[0], co[1] - gp[1], co[2] - gp[2]};
+            mattvec3(r + RR_FRAME, gR, d0);
+            mattvec3(r + RR_FRAME + 3, gR, cx);
+            mattvec3(r + RR_FRAME + 6, gR, cy);
+            mattvec3(r + RR_FRAME + 9, gR, cz);
+            // the light in the geom frame: its direction, or its position
+            const float lv[3] = {L.directional ? L.v[0] : L.v[0] - gp[0], L.directional ? L.v[1] : L.v[1] - gp[1],
+                                 L.directional ? L.v[2] : L.v[2] - gp[2]};
+            mattvec3(r + SR_LIGHT, gR, lv);
+            r[SR_LIGHT + 3] = 0.f;
+          }
+          __syncthreads();
+          survivors += total;
+          // stage two
+          if (wave_on) {
+            const float tmax = L.directional ? RINF : 1.0f;  // (a positional light's ray is not normalised)
+            for (int k = 0; k < total; k++) {
+              const float* r = rec + k * DX_SHADE_REC;
+              const float* F = r + RR_FRAME;
+              const float o[3] = {F[0] + t * (F[3] * u - F[6] * v - F[9]), F[1] + t * (F[4] * u - F[7] * v - F[10]),
+                                  F[2] + t * (F[5] * u - F[8] * v - F[11])};
+              const float d[3] = {L.directional ? r[SR_LIGHT] : r[SR_LIGHT] - o[0],
+                                  L.directional ? r[SR_LIGHT + 1] : r[SR_LIGHT + 1] - o[1],
+                                  L.directional ? r[SR_LIGHT + 2] : r[SR_LIGHT + 2] - o[2]};
+              const float tau = geom_entry(r, o, d, A);
+              occl = occl || (need && rec_int(r, RR_GEOM) != g && tau > 0.f && tau < tmax);
+            }
+          }
+          __syncthreads();  // the list and wcnt are reused
+        }
+      }
+    }
+    const bool lit = ndl > 0.f && !occl;
+    for (int k = 0; k < 3; k++) E[k] += lit ? L.diffuse[k] * ndl : 0.f;
+  }
+
+  // albedo: the geom's colour, a registered box's face colour, the plane's checker
+  float alb[3] = {SA.geom_rgb[3 * gi], SA.geom_rgb[3 * gi + 1], SA.geom_rgb[3 * gi + 2]};
+  if (type == DXG_BOX) {
+    const float* faces = SA.geom_rgb + 3 * (size_t)A.ngeom;
+    for (int k = 0; k < S.nface; k++)
+      if (S.face_geom[k] == g)
+        for (int c = 0; c < 3; c++) alb[c] = faces[(k * 6 + face) * 3 + c];
+  }
+  if (type == DXG_PLANE && S.checker_cell > 0.f) {
+    const int par = ((int)floorf(p[0] / S.checker_cell) + (int)floorf(p[1] / S.checker_cell)) & 1;
+    for (int c = 0; c < 3; c++) alb[c] = S.checker_rgb[par][c];
+  }
+  for (int c = 0; c < 3; c++)
+    trgb[(ly * DX_RENDER_TILE + lx) * 3 + c] =
+        (unsigned char)colour_byte(hit ? alb[c] * fminf(1.0f, E[c]) : S.background[c]);
+  __syncthreads();
+
+  // a row segment of the tile is up to 48 contiguous bytes of the image: whole dwords where
+  // the image's own alignment allows, single bytes at a segment's unaligned ends
+  {
+    const int row = tid / 13, j = tid % 13, y = ty0 + row;
+    if (row < DX_RENDER_TILE && y < A.H) {
+      const size_t start = ((((size_t)env * A.ncam + cam) * A.H + y) * A.W + tx0) * 3;
+      const size_t end = start + (size_t)min(DX_RENDER_TILE, A.W - tx0) * 3;
+      const size_t a = (start & ~(size_t)3) + 4 * (size_t)j;
+      const unsigned char* src = trgb + row * DX_RENDER_TILE * 3;
+      if (a >= start && a + 4 <= end) {
+        const size_t i = a - start;
+        const unsigned val = (unsigned)src[i] | ((unsigned)src[i + 1] << 8) | ((unsigned)src[i + 2] << 16) | ((unsigned)src[i + 3] << 24);
+        *reinterpret_cast<unsigned*>(SA.rgb + a) = val;
+      } else {
+        for (int q = 0; q < 4; q++)
+          if (a + q >= start && a + q < end) SA.rgb[a + q] = src[a + q - start];
+      }
+    }
+  }
+  if (SA.stats && tid == 0 && passes) {
+    atomicAdd(SA.stats, (unsigned long long)survivors);
+    atomicMax(SA.stats + 1, (unsigned long long)survivors);
+    atomicAdd(SA.stats + 2, (unsigned long long)passes);
+  }
+}
+
+hipError_t dx_launch_shade(hipStream_t stream, const ShadeArgs& A) {
+  const size_t grid = (size_t)A.R.nenv * A.R.ncam * A.R.tiles_x * A.R.tiles_y;
+  hipLaunchKernelGGL(dx_shade_kernel, dim3((unsigned)grid), dim3(DX_RENDER_THREADS), 0, stream, A);
+  return hipGetLastError();
 }
 
 hipError_t dx_launch_render(hipStream_t stream, const RenderArgs& A) {

@@ -610,6 +610,8 @@ class GoalEnvironment:
                 if o["segmentation"]:
                     spec[f"{name}_segmentation"] = Array((o["height"], o["width"], 2), np.int32,
                                                          name=f"{name}_segmentation")
+                if o.get("rgb"):
+                    spec[f"{name}_rgb"] = BoundedArray((o["height"], o["width"], 3), np.uint8, 0, 255, name=f"{name}_rgb")
         return spec
 
     # ---------------------------------------------------------------- stepping
@@ -810,7 +812,8 @@ class GoalEnvironment:
 
     # ---------------------------------------------------------------- cameras
     def enable_cameras(self, configs_or_names, height: int = 84, width: int = 84, depth: bool = True,
-                       segmentation: bool = False, near: float = 0.01, far: float = 10.0) -> None:
+                       segmentation: bool = False, near: float = 0.01, far: float = 10.0, rgb: bool = False,
+                       shading: Optional[dict] = None) -> None:
         """The reference's camera observables (manipulation/shared/cameras.py:53-64 at the
         84 x 84 spec of observations.py:62-74) as depth and segmentation images, ray cast on
         the device behind every control step (include/dx.h dx_env_set_cameras).  Cameras are
@@ -820,28 +823,64 @@ class GoalEnvironment:
           f"{name}_depth"         [B, H, W, 1] float32, metres along the optical axis, `far`
                                   where nothing is seen (dm_control's depth=True);
           f"{name}_segmentation"  [B, H, W, 2] int32, (geom id, 5 = mjOBJ_GEOM), or (-1, -1)
-                                  where nothing is seen (dm_control's segmentation=True).
+                                  where nothing is seen (dm_control's segmentation=True);
+          f"{name}_rgb"           [B, H, W, 3] uint8 (`rgb=True`: dm_control's default camera
+                                  output), shaded by the model include/dx.h states under
+                                  "Shaded RGB" -- flat per hull facet, no textures, colours a
+                                  runtime input.  `shading` holds `set_shading`'s keywords
+                                  (geom_rgb, box_faces, lights, shading); None keeps the
+                                  settings in force, the defaults at first.
         They describe the same state as the rest of the observation, also for an env that
         returned FIRST, and right after this call.  Only the compiled (collision) geoms
-        exist; there is no RGB.  The packed rows, the observation pipeline and the
-        checkpoint do not carry the images.  Bad options raise ValueError."""
+        exist.  The packed rows, the observation pipeline and the checkpoint do not carry
+        the images.  Bad options raise ValueError."""
         cfgs = cameras_lib.resolve(configs_or_names)
         if not cfgs:
             _lib.check(_lib.load().dx_env_set_cameras(self.ptr, None, 0, 0, 0, 0))
             self.camera_options = None
+            self.physics._cameras = ()
             return
         bodies = cameras_lib.validate(cfgs, width, height, depth, segmentation, near, far, self.num_envs,
-                                      self.task.compiled.names["body"])
+                                      self.task.compiled.names["body"], rgb=rgb)
+        if rgb and (shading is not None or not getattr(self, "_shading_set", False)):
+            self.set_shading(**(shading or {}))
         arr = (_lib.Camera * len(cfgs))()
         for c, cfg, body in zip(arr, cfgs, bodies):
             c.pos[:] = [float(v) for v in cfg.pos]
             c.xyaxes[:] = [float(v) for v in cfg.xyaxes]
             c.fovy, c.near_, c.far_, c.body = float(cfg.fovy), float(near), float(far), body
-        flags = (_lib.RENDER_DEPTH if depth else 0) | (_lib.RENDER_SEGMENTATION if segmentation else 0)
+        flags = (_lib.RENDER_DEPTH if depth else 0) | (_lib.RENDER_SEGMENTATION if segmentation else 0) | \
+            (_lib.RENDER_RGB if rgb else 0)
         _lib.check(_lib.load().dx_env_set_cameras(self.ptr, arr, len(cfgs), int(width), int(height), flags))
         self.camera_options = dict(names=tuple(c.name for c in cfgs), configs=tuple(cfgs), height=int(height),
                                    width=int(width), depth=bool(depth), segmentation=bool(segmentation),
-                                   near=float(near), far=float(far))
+                                   near=float(near), far=float(far), rgb=bool(rgb))
+        # (the borrowed batch handle's host copies -- physics.rgb() -- read the same images)
+        self.physics._cameras = tuple(cfgs)
+        self.physics._camera_shape = (self.num_envs, len(cfgs), int(height), int(width))
+
+    def set_shading(self, geom_rgb=None, box_faces=None, lights=None, shading=None) -> None:
+        """The shading settings of the RGB images (`BatchedPhysics.set_shading`'s arguments;
+        include/dx.h dx_env_set_shading).  They persist across `enable_cameras`; images that
+        are on are rendered afresh.  Bad settings raise ValueError before any library call."""
+        cm = self.task.compiled
+        if geom_rgb is None and box_faces is None:
+            geom_rgb, box_faces = cameras_lib.default_palette(cm)
+        elif geom_rgb is None:
+            geom_rgb = cameras_lib.default_palette(cm)[0]
+        elif box_faces is None:
+            box_faces = {}
+        parts = cameras_lib.validate_shading(geom_rgb, box_faces, cameras_lib.DEFAULT_LIGHTS if lights is None else lights,
+                                             cameras_lib.DEFAULT_SHADING if shading is None else shading,
+                                             np.asarray(cm.geom_type))
+        args, keep = _lib.shading_args(*parts)
+        _lib.check(_lib.load().dx_env_set_shading(self.ptr, *args))
+        del keep
+        self._shading_set = True
+
+    def rgb_ptr(self) -> int:
+        """Device address of the [num_envs, ncam, H, W, 3] uint8 RGB images (while enabled)."""
+        return self._out(_lib.OUT_RGB)
 
     def depth_ptr(self) -> int:
         """Device address of the [num_envs, ncam, H, W] float32 depth images (while enabled)."""
@@ -862,6 +901,7 @@ class GoalEnvironment:
         shape = (self.num_envs, len(o["names"]), o["height"], o["width"])
         dep = self._read(_lib.OUT_DEPTH, np.float32, n).reshape(shape) if o["depth"] else None
         seg = self._read(_lib.OUT_SEGMENTATION, np.int32, n).reshape(shape) if o["segmentation"] else None
+        rgb = self._read(_lib.OUT_RGB, np.uint8, 3 * n).reshape(shape + (3,)) if o.get("rgb") else None
         for k, name in enumerate(o["names"]):
             if dep is not None:
                 out[f"{name}_depth"] = dep[:, k, :, :, None].copy()
@@ -869,6 +909,8 @@ class GoalEnvironment:
                 s = seg[:, k]
                 out[f"{name}_segmentation"] = np.stack([s, np.where(s >= 0, cameras_lib.OBJ_GEOM, -1)],
                                                        axis=-1).astype(np.int32)
+            if rgb is not None:
+                out[f"{name}_rgb"] = rgb[:, k].copy()
         return out
 
     # ---------------------------------------------------------------- random pushes
@@ -1175,8 +1217,8 @@ def load(domain_name: str, task_name: str, seed: Optional[int] = None,
     loaded with seed `seed + env_offset + e`; `env_offset` places a shard of a sharded
     job (distributed.env_shard) in the job's env numbering.  The last four arguments are
     `GoalEnvironment.configure_actions`' (default: the action pipeline off).  `cameras`
-    (CameraConfigs or names) and `camera_options` (height, width, depth, segmentation, near,
-    far) are `GoalEnvironment.enable_cameras`' (default: no cameras)."""
+    (CameraConfigs or names) and `camera_options` (height, width, depth, segmentation, rgb,
+    shading, near, far) are `GoalEnvironment.enable_cameras`' (default: no cameras)."""
     key = (domain_name, task_name)
     if domain_name not in {d for d, _ in SUITE}:
         raise ValueError(f"Unknown domain: {domain_name}")

@@ -234,11 +234,12 @@ class BatchedPhysics:
     # ------------------------------------------------------------------ #
     # depth / segmentation cameras and batched rays (include/dx.h dx_render_set_cameras)
     def set_cameras(self, configs, width: int, height: int, depth: bool = True, segmentation: bool = False,
-                    near: float = 0.01, far: float = 10.0, cull: bool = True) -> None:
+                    near: float = 0.01, far: float = 10.0, cull: bool = True, rgb: bool = False) -> None:
         """The cameras `render()` casts: CameraConfigs or names of the five of
         `dexterity_amd.cameras` (an empty list switches them off).  Depth is the distance
         along the optical axis in metres, `far` on a miss; segmentation the geom id, -1 on a
-        miss.  `cull=False` renders without the per-tile geom cull (the same images).  Bad
+        miss; rgb the shaded uint8 image (`set_shading`; include/dx.h "Shaded RGB").
+        `cull=False` renders without the per-tile geom culls (the same images).  Bad
         options raise ValueError before any library call."""
         cfgs = cameras_lib.resolve(configs)
         L = _lib.load()
@@ -247,14 +248,14 @@ class BatchedPhysics:
             self._cameras = ()
             return
         bodies = cameras_lib.validate(cfgs, width, height, depth, segmentation, near, far, self.nenv,
-                                      self.model.compiled.names["body"])
+                                      self.model.compiled.names["body"], rgb=rgb)
         arr = (_lib.Camera * len(cfgs))()
         for c, cfg, body in zip(arr, cfgs, bodies):
             c.pos[:] = [float(v) for v in cfg.pos]
             c.xyaxes[:] = [float(v) for v in cfg.xyaxes]
             c.fovy, c.near_, c.far_, c.body = float(cfg.fovy), float(near), float(far), body
         flags = (_lib.RENDER_DEPTH if depth else 0) | (_lib.RENDER_SEGMENTATION if segmentation else 0) | \
-            (0 if cull else _lib.RENDER_NO_CULL)
+            (0 if cull else _lib.RENDER_NO_CULL) | (_lib.RENDER_RGB if rgb else 0)
         _lib.check(L.dx_render_set_cameras(self.ptr, arr, len(cfgs), int(width), int(height), flags))
         self._cameras = tuple(cfgs)
         self._camera_shape = (self.nenv, len(cfgs), int(height), int(width))
@@ -278,8 +279,46 @@ class BatchedPhysics:
         """[B, ncam, H, W] int32 host copy of the last render's geom ids (-1: none)."""
         return self._image(_lib.RENDER_SEGMENTATION, np.int32)
 
+    def set_shading(self, geom_rgb=None, box_faces=None, lights=None, shading=None) -> None:
+        """The settings of the shaded RGB images (include/dx.h dx_render_set_shading); they
+        persist across `set_cameras`.  geom_rgb [ngeom, 3] linear colours; box_faces {box geom
+        id: [6, 3]} face colours in the order +x, -x, +y, -y, +z, -z; lights a sequence of
+        `cameras.Light` (at most 4); shading a `cameras.Shading`.  None is that part's default
+        (`cameras.default_palette`, `DEFAULT_LIGHTS`, `DEFAULT_SHADING`).  Bad settings raise
+        ValueError before any library call."""
+        cm = self.model.compiled
+        if geom_rgb is None and box_faces is None:
+            geom_rgb, box_faces = cameras_lib.default_palette(cm)
+        elif geom_rgb is None:
+            geom_rgb = cameras_lib.default_palette(cm)[0]
+        elif box_faces is None:
+            box_faces = {}
+        parts = cameras_lib.validate_shading(geom_rgb, box_faces, cameras_lib.DEFAULT_LIGHTS if lights is None else lights,
+                                             cameras_lib.DEFAULT_SHADING if shading is None else shading,
+                                             np.asarray(cm.geom_type))
+        args, keep = _lib.shading_args(*parts)
+        _lib.check(_lib.load().dx_render_set_shading(self.ptr, *args))
+        del keep
+
+    def rgb(self) -> np.ndarray:
+        """[B, ncam, H, W, 3] uint8 host copy of the last render's shaded images."""
+        if not getattr(self, "_cameras", ()):
+            raise _lib.DxError("no cameras (set_cameras)")
+        out = np.empty(self._camera_shape + (3,), dtype=np.uint8)
+        _lib.check(_lib.load().dx_render_get(self.ptr, _lib.RENDER_RGB, out.ctypes.data, 0, self.nenv))
+        return out
+
+    def shadow_stats(self):
+        """(survivors summed, their maximum, passes) of the shading pass's shadow cull since the
+        last call: the geoms per pixel tile and shadow-casting light that survive it
+        (`render_stats` switches the counting on)."""
+        out = (ctypes.c_uint64 * 3)()
+        _lib.check(_lib.load().dx_render_stats2(self.ptr, out))
+        return tuple(int(v) for v in out)
+
     def image_ptr(self, which: int) -> int:
-        """Device address of the depth (`_lib.RENDER_DEPTH`) or segmentation images."""
+        """Device address of the depth (`_lib.RENDER_DEPTH`), segmentation or RGB
+        (`_lib.RENDER_RGB`) images."""
         p = ctypes.c_void_p()
         _lib.check(_lib.load().dx_render_output(self.ptr, which, ctypes.byref(p)))
         return p.value

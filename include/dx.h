@@ -299,7 +299,9 @@ enum dx_env_out { DX_OUT_OBS = 0, DX_OUT_REWARD = 1, DX_OUT_DISCOUNT = 2, DX_OUT
                                        cameras with DX_RENDER_DEPTH are on (dx_env_set_cameras) */,
                   DX_OUT_SEGMENTATION = 14 /* [nenv][ncam][H][W] int32, the geom id each pixel sees
                                               (-1: none); while cameras with DX_RENDER_SEGMENTATION
-                                              are on */ };
+                                              are on */,
+                  DX_OUT_RGB = 15 /* [nenv][ncam][H][W][3] uint8, the shaded images; while cameras
+                                     with DX_RENDER_RGB are on */ };
 dx_env* dx_env_create(const dx_model* m, int32_t nenv, int32_t device, int32_t task, uint64_t seed,
                       const float* params, int32_t nparams);
 /* One shard of a job's environments: this handle's env e is the job's env env0 + e.
@@ -701,7 +703,8 @@ int dx_dls_map(dx_batch* b, const int32_t* types, const int32_t* ids, int32_t no
 /* The reference's vision observables (manipulation/shared/observations.py:62-111, the 84 x 84
  * camera spec with its `depth` and `segmentation` switches; cameras.py:22-50) as a ray cast
  * against the geoms the compiled model holds -- the plane, boxes, spheres, capsules and
- * convex hulls -- in one launch behind the step (dx_render.hip).  Shaded RGB is not built.
+ * convex hulls -- in one launch behind the step (dx_render.hip).  Shaded RGB images come from
+ * a second launch over the same cast (below: "Shaded RGB").
  *
  * Camera model ([3P] MuJoCo's pinhole).  The frame comes from xyaxes: x normalised, y made
  * orthogonal to x and normalised, z = x (x) y; the camera looks along -z.  fovy is the
@@ -732,7 +735,7 @@ int dx_dls_map(dx_batch* b, const int32_t* types, const int32_t* ids, int32_t no
  * out as (nx, ny, nz, d), unit n, n.x + d <= 0 inside, geom frame, and returns the count.
  *
  * dx_render_set_cameras: flags selects the outputs (at least one of DX_RENDER_DEPTH,
- * DX_RENDER_SEGMENTATION); DX_RENDER_NO_CULL renders without the per-tile geom cull and
+ * DX_RENDER_SEGMENTATION, DX_RENDER_RGB); DX_RENDER_NO_CULL renders without the per-tile geom cull and
  * gives bit-identical images (a test and measurement switch).  ncam = 0 switches the
  * feature off and frees nothing a later call would need.  While cameras are on the batch
  * writes body poses (dx_set_outputs(batch, 1); the earlier setting is restored when they
@@ -766,9 +769,11 @@ typedef struct dx_camera {
   float near_, far_;     /* metres along the optical axis */
   int32_t body;          /* -1: world-fixed */
 } dx_camera;
-enum { DX_RENDER_DEPTH = 1, DX_RENDER_SEGMENTATION = 2, DX_RENDER_NO_CULL = 4 };
+enum { DX_RENDER_DEPTH = 1, DX_RENDER_SEGMENTATION = 2, DX_RENDER_NO_CULL = 4, DX_RENDER_RGB = 8 };
 #define DX_RENDER_MAX_CAMERAS 8
 #define DX_RENDER_MAX_SIDE 512
+#define DX_RENDER_MAX_LIGHTS 4
+#define DX_RENDER_MAX_FACE_GEOMS 8
 int dx_model_hull_planes(const dx_model* m, int32_t mesh, float* out /* [n][4] or NULL */, int32_t n);
 int dx_render_set_cameras(dx_batch* b, const dx_camera* cams, int32_t ncam, int32_t width, int32_t height,
                           int32_t flags);
@@ -779,7 +784,7 @@ int dx_render_stats(dx_batch* b, int enable, uint64_t out[3]);
 int dx_ray(dx_batch* b, const float* origin, const float* dir, int32_t nray, float* dist, int32_t* geom);
 /* Env level: the cameras of a dx_env's batch, rendered behind every call that produces the
  * observation (dx_env_reset, dx_env_step, dx_env_step_random, dx_env_step_host), after its
- * last launch: DX_OUT_DEPTH / DX_OUT_SEGMENTATION describe the same state as DX_OUT_OBS, and an
+ * last launch: DX_OUT_DEPTH / DX_OUT_SEGMENTATION / DX_OUT_RGB describe the same state as DX_OUT_OBS, and an
  * env that returned FIRST shows its reset state.  dx_env_set_cameras may be called between
  * steps and leaves the images holding the current state; ncam = 0 switches them off (the
  * default: a control step then launches what it launched before, and dx_env_output of the two
@@ -788,6 +793,69 @@ int dx_ray(dx_batch* b, const float* origin, const float* dir, int32_t nray, flo
  * step or reset. */
 int dx_env_set_cameras(dx_env* e, const dx_camera* cams, int32_t ncam, int32_t width, int32_t height,
                        int32_t flags);
+
+/* Shaded RGB -------------------------------------------------------------- */
+/* DX_RENDER_RGB adds [nenv][ncam][height][width][3] uint8 images (dx_render_output /
+ * dx_render_get with which = DX_RENDER_RGB; DX_OUT_RGB at the env level), shaded by a second
+ * kernel behind the cast, which reads the cast's depth and geom id per pixel.  With
+ * DX_RENDER_RGB alone the cast still runs, into buffers of the library's own: DX_RENDER_DEPTH
+ * and DX_RENDER_SEGMENTATION then stay "not enabled".  The exact contracts of the cast hold
+ * for the bytes too (cull, tiling, other cameras, two renders).
+ *
+ * The shading model (written down so that a numpy restatement pins it; it is not OpenGL's).
+ * With O the camera origin, D the pixel's unnormalised direction and t the cast's depth,
+ * P = O + t D is the hit point and p the same point in the hit geom's frame.
+ *  Normal, from p alone: plane +z; sphere p/|p|; capsule q/|q| with q = p - clamp(p_z, -h, h) e_z;
+ *   box: axis k = argmax_k (|p_k| - size_k), lowest k on a tie, n = sign(p_k) e_k, face
+ *   f = 2k + (p_k < 0) (+x, -x, +y, -y, +z, -z); hull: the normal of the face plane with the
+ *   largest n_i.p + d_i (dx_model_hull_planes' planes, lowest index on a tie): flat per facet.
+ *   The geom's pose turns it to the world.
+ *  Lights (at most DX_RENDER_MAX_LIGHTS): l = -dir/|dir| for a directional light, else
+ *   (pos - P)/|pos - P|.  The optional headlight has l = the camera's +z axis for every pixel
+ *   and casts no shadow.
+ *  Shadows: a light with castshadow does not reach a pixel with n.l > 0 when the line
+ *   P + tau l enters a geom other than the hit one at 0 < tau < tau_max (infinity for a
+ *   directional light, |pos - P| else); "enters" is the cast's own entry test, so an entry at
+ *   tau <= 0 does not occlude and a hull thinner than the cast resolves casts no shadow.
+ *   Every geom is convex and shadows itself exactly where n.l <= 0: no bias, no epsilon.
+ *  Colour, linear (no gamma, no specular term):
+ *   c = albedo * min(1, ambient + sum_l s_l diffuse_l max(0, n.l_l)), stored as
+ *   floor(255 c + 0.5) clamped to 0..255; a miss stores `background`.
+ *  Albedo: geom_rgb[g]; for a box registered in face_geom, face_rgb[slot][f]; for a plane geom
+ *   with checker_cell > 0, checker_rgb[(floor(p_x / cell) + floor(p_y / cell)) & 1].
+ * No alpha, textures, materials, highlights, reflectance, skybox or visual meshes.
+ *
+ * dx_render_set_shading: the settings persist across dx_render_set_cameras and may be given
+ * before or after it; without a call the defaults hold.  geom_rgb NULL: the default palette --
+ * the world's geoms (0.45, 0.45, 0.5), the geoms of each hand (a tree whose root has no free
+ * joint, in root order) (0.85, 0.65, 0.5) or (0.5, 0.65, 0.85) in turn, a free-jointed prop's
+ * (0.8, 0.8, 0.8) -- and, when face_geom is NULL too, the first box geom of a free-jointed body
+ * with the six face colours red, green, blue, yellow, magenta, cyan (dexterity_amd/cameras.py
+ * holds the values).  face_geom non-NULL with nface = 0: no face colours.  lights NULL: the
+ * reference arena's light, directional, straight down (dir (0, 0, -1)), diffuse 0.5,
+ * castshadow; lights non-NULL with nlight = 0: no lights.  shading NULL: ambient 0.2,
+ * background 0, headlight 0.3 ([3P] MuJoCo's default headlight is on), no checker.  DX_EINVAL: a face_geom that is no box geom or is repeated, a
+ * non-finite value, a negative checker_cell, a zero dir on a directional light, a null array
+ * with a positive count; DX_ELIMIT: more than DX_RENDER_MAX_LIGHTS lights or
+ * DX_RENDER_MAX_FACE_GEOMS face geoms.  It synchronises the stream; a refused call changes nothing.
+ * dx_render_stats2 (measurement): as dx_render_stats, for the shadow pass's cull (geoms that
+ * survive per pixel tile and shadow-casting light); one switch serves both. */
+typedef struct dx_light {
+  float pos[3], dir[3], diffuse[3];
+  int32_t directional, castshadow;
+} dx_light;
+typedef struct dx_shading {
+  float ambient[3], background[3];
+  float headlight[3];      /* diffuse; all 0 = off */
+  float checker_rgb[2][3];
+  float checker_cell;      /* metres; 0 = off */
+} dx_shading;
+int dx_render_set_shading(dx_batch* b, const float* geom_rgb /* [ngeom][3] or NULL */, const int32_t* face_geom,
+                          const float* face_rgb /* [nface][6][3] */, int32_t nface, const dx_light* lights,
+                          int32_t nlight, const dx_shading* shading /* or NULL */);
+int dx_env_set_shading(dx_env* e, const float* geom_rgb, const int32_t* face_geom, const float* face_rgb,
+                       int32_t nface, const dx_light* lights, int32_t nlight, const dx_shading* shading);
+int dx_render_stats2(dx_batch* b, uint64_t out[3]);
 
 /* Timing ---------------------------------------------------------------- */
 /* When enabled, HIP events bracket the step-kernel launches on the batch stream -- every

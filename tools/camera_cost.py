@@ -3,8 +3,10 @@
 Per camera (`front_close`, and the close `near_top` of the tests) and per cull setting:
 HIP-event time of each of 100 renders behind 10 warm-up renders, and the geoms that survive
 the per-tile cull (mean and maximum per tile).  Beside them the control step's wall-clock ms
-with cameras off and on (one synchronisation at the end of the timed steps).  One JSON line
-per case.
+with cameras off and on (one synchronisation at the end of the timed steps).  Ahead of them,
+per camera, depth only against depth + shaded RGB under the default lights (one shadow-casting
+light): ms per control step, ms per render, and the geoms that survive the shadow cull per
+tile.  One JSON line per case.
 
     python tools/camera_cost.py [--envs 4096] [--side 84] [--renders 100] [--steps 200]
 """
@@ -67,6 +69,7 @@ def main():
     ap.add_argument("--renders", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--rgb-only", action="store_true", help="only the depth against depth + RGB rows")
     a = ap.parse_args()
     L = _lib.load()
     hip = manipulation._hip_runtime()
@@ -80,7 +83,28 @@ def main():
     print(json.dumps({"config": f"3 reorient {a.envs}, cameras off", "ms_per_step": round(off_ms, 4)}), flush=True)
     stream = ctypes.c_void_p(L.dx_stream(env.physics.ptr))
     tiles = ((a.side + 15) // 16) ** 2
+    # depth only against depth + RGB under the default lights (one shadow-casting light)
     for cam in CAMERAS:
+        row = {"config": f"3 reorient {a.envs}, {cam.name} {a.side}x{a.side}: depth only / depth + RGB"}
+        for rgb in (False, True):
+            env.enable_cameras([cam], height=a.side, width=a.side, depth=True, segmentation=False, rgb=rgb)
+            row["ms_per_step_depth_rgb" if rgb else "ms_per_step_depth"] = round(step_ms(env, k, a.steps), 4)
+            k += a.steps
+            env.physics.set_cameras([cam], a.side, a.side, depth=True, segmentation=False, rgb=rgb)
+            for _ in range(10):
+                env.physics.render()
+            ms = event_times(hip, stream, env.physics.render, a.renders)
+            row["render_ms_mean_depth_rgb" if rgb else "render_ms_mean_depth"] = round(sum(ms) / len(ms), 4)
+        env.physics.render_stats(True)
+        env.physics.shadow_stats()
+        env.physics.render()
+        env.physics.render_stats(False)
+        total, most, passes = env.physics.shadow_stats()
+        row.update(ms_per_step_cameras_off=round(off_ms, 4), shadow_survivors_per_tile_mean=round(total / max(passes, 1), 2),
+                   shadow_survivors_per_tile_max=most, shadow_passes=passes, tiles=a.envs * tiles)
+        print(json.dumps(row), flush=True)
+        env.enable_cameras([])
+    for cam in () if a.rgb_only else CAMERAS:
         env.enable_cameras([cam], height=a.side, width=a.side, depth=True, segmentation=True)
         on_ms = step_ms(env, k, a.steps)
         k += a.steps
